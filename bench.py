@@ -20,6 +20,12 @@ barriers around the timed region and the slowest rank's time is reported.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--producers P]
                     [--mode rgba|rgb] [--consumer none|disc] [--codec none|tile16]
                     [--h2d auto|copy] [--graph auto|on|off] [--dist shard|pool|scatter]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints; --full adds the
+"sustained" window (about --sustain-s more seconds of steps, reported next to
+the headline figure).  --dump-outputs DIR writes the last timed step's batch
+(and loss) as DIR/<name>.npy from fixed-pose frames, the same in every run.
 
 --consumer disc adds a DCGAN discriminator training step per batch (bf16,
 fused gfx950 BN+LeakyReLU and pooling kernels, fused Adam, one HIP graph per
@@ -53,14 +59,32 @@ BASELINE_NOTE = ('vs_baseline = value / 90.9 img/s, the reference\'s best row: 5
 
 
 def ensure_built():
-    """Incremental in-tree build, serialised across ranks with a file lock."""
+    """Incremental in-tree build, serialised across ranks with a file lock.
+
+    A tree this user cannot write to (built by someone else, or mounted
+    read-only) cannot be rebuilt: it runs as built, and a missing extension or
+    producer is an error here instead of a failed compile."""
     from blendtorch import _build
+
+    def run_as_built():
+        pkg = PKG / 'blendtorch'
+        need = [pkg / 'bin' / 'cubesim'] + [pkg / (m + _build._ext_suffix()) for m in ('_native', '_hip')]
+        missing = [str(p) for p in need if not p.exists()]
+        if missing:
+            raise RuntimeError(f'{ROOT} is not writable and not built (python -m blendtorch._build): {missing}')
+
     lock = ROOT / 'build' / '.bench.lock'
-    lock.parent.mkdir(parents=True, exist_ok=True)
-    with open(lock, 'w') as fp:
+    try:
+        lock.parent.mkdir(parents=True, exist_ok=True)
+        fp = open(lock, 'w')
+    except OSError:
+        return run_as_built()
+    with fp:
         fcntl.flock(fp, fcntl.LOCK_EX)
         try:
             _build.build_all()
+        except PermissionError:
+            run_as_built()
         finally:
             fcntl.flock(fp, fcntl.LOCK_UN)
 
@@ -163,9 +187,20 @@ def parse_args(argv=None):
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
                     help='process-group backend (nccl = RCCL over xGMI; gloo only to rehearse several ranks on one GPU)')
     ap.add_argument('--start-port', type=int, default=0)
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the "sustained" window after the timed '
+                         'steps (--sustain-s).  A plain run sets up, warms up, times --steps steps and prints')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned to its caller as '
+                         'DIR/<name>.npy (float32; image = the batch tensor, loss = the disc consumer\'s loss; at '
+                         'most 64 MB in all, a seeded sample of anything larger).  The producers then render one '
+                         'fixed pose (cubesim --rotation) instead of random ones, so every frame -- whichever '
+                         'producer it came from and in whatever order -- and with it the dump is the same from '
+                         'run to run; the disc consumer also warms up for exactly --warmup steps (its loss then '
+                         'differs between runs only by the training step\'s own floating-point reduction order)')
     ap.add_argument('--sustain-s', type=float, default=2.0,
-                    help='after the timed steps, time about this many more seconds of steps and report them as '
-                         '"sustained" (a short timed window is served from the warm-up backlog); 0: off')
+                    help='with --full: after the timed steps, time about this many more seconds of steps and report '
+                         'them as "sustained" (a short timed window is served from the warm-up backlog); 0: off')
     ap.add_argument('--host-sync', choices=['auto', 'on', 'off'], default='auto',
                     help='loader/consumer ordering by host-side event checks (on) or cross-stream waits (off); '
                          'auto = on (a stream of cross-stream waits keeps a HIP runtime thread busy: 43 -> 20 '
@@ -253,6 +288,36 @@ def supervise(args, argv) -> int:
 
 def _r(v, nd):
     return None if v is None else round(v, nd)
+
+
+# --dump-outputs: one pose for every frame of every producer (Euler XYZ, radians)
+DUMP_ROTATION = ('0.6', '0.4', '0.9')
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """Write {name: tensor} as out_dir/<name>.npy (float32; rank r > 0:
+    <name>.rank<r>.npy).  The arrays share DUMP_BUDGET_BYTES (per rank: / world);
+    one that exceeds its share is written as a fixed, seeded sample of its
+    flattened elements (sorted indices, the same for every run and build)."""
+    import numpy as np
+    import torch
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // max(1, world) // 4      # float32 elements this rank may write
+    written = {}
+    # smallest first: an array below its even share of what is left passes the rest on
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        a = t.detach().to(torch.float32).cpu().contiguous().numpy()
+        share = left // (len(arrays) - i)
+        left -= min(a.size, share)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        path = out_dir / (f'{name}.npy' if rank == 0 else f'{name}.rank{rank}.npy')
+        np.save(path, a)
+        written[path.name] = list(a.shape)
+    return written
 
 
 def main(argv=None):
@@ -399,6 +464,9 @@ def main(argv=None):
                   instance_args=[['--mode', args.mode, '--sndhwm', '10', '--resolution', f'{res_w}x{res_h}']
                                  + (['--shm', str(shm_slots), '--codec', args.codec]
                                     if shm_slots and i >= args.inline_producers else [])
+                                 # --dump-outputs: identical frames, so the batches do not
+                                 # depend on how the producers' streams interleave
+                                 + (['--rotation', *DUMP_ROTATION] if args.dump_outputs else [])
                                  for i in range(nprod)])
     model = opt = None
     copy_streams = args.copy_streams or (1 if args.consumer == 'disc' else 2)
@@ -431,7 +499,8 @@ def main(argv=None):
         crit = torch.nn.BCELoss()
 
     WARM_RESERVE = 2000   # extra warm-up batches allowed while producers come up
-    SUSTAIN_RESERVE = 12000 if args.sustain_s > 0 else 0   # batches the sustained window may draw (bound only)
+    sustain = args.full and args.sustain_s > 0
+    SUSTAIN_RESERVE = 12000 if sustain else 0   # batches the sustained window may draw (bound only)
     total_batches = args.warmup + args.steps + (WARM_RESERVE + SUSTAIN_RESERVE if args.dist != 'scatter' else 0)
     last = {'btid': None}
     from contextlib import ExitStack
@@ -549,7 +618,9 @@ def main(argv=None):
         # has delivered a frame, so the timed region starts in steady state on every rank
         seen = set()
         n_warm, t_warm = 0, time.time()
-        while n_warm < args.warmup or (args.dist != 'scatter' and len(seen) < nprod and n_warm < WARM_RESERVE
+        # (--dump-outputs with a training consumer: exactly W steps, the dumped loss depends on their number)
+        wait_all = args.dist != 'scatter' and not (args.dump_outputs and model is not None)
+        while n_warm < args.warmup or (wait_all and len(seen) < nprod and n_warm < WARM_RESERVE
                                        and time.time() - t_warm < 20):
             step()
             n_warm += 1
@@ -576,6 +647,14 @@ def main(argv=None):
         snap1 = dl.snapshot() if dl is not None else {}
         ru1 = os.times()
         cg1 = cgroup_cpu_stat()
+        dumped = None
+        if args.dump_outputs:
+            # what the last timed step handed to its caller: the batch tensor, and the
+            # training consumer's loss (the loader re-posts its tensors, so write them now)
+            outs = {'image': img}
+            if stepper is not None and stepper.last_losses():
+                outs['loss'] = stepper.last_losses()[-1].reshape(-1)
+            dumped = dump_outputs(args.dump_outputs, outs, rank, world)
         # Sustained rate, reported next to (never instead of) the timed K steps:
         # a short driver window (e.g. 20 steps) is served from the frames the
         # producers queued during warm-up (backlog_covers_window), so the same
@@ -583,7 +662,7 @@ def main(argv=None):
         # cannot cover, with its own loader window.  Every rank runs the same
         # number of steps (the data-parallel step all-reduces per step).
         sustained = None
-        if args.sustain_s > 0 and args.dist != 'scatter':
+        if sustain and args.dist != 'scatter':
             te = torch.tensor([elapsed], dtype=torch.float64, device=pg_dev)
             if world > 1:
                 dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -693,7 +772,8 @@ def main(argv=None):
                             'max': round(max(r['elapsed_s'] for r in per_rank), 6)},
             'per_rank': per_rank,
             'dtype': 'bf16' if amp else 'fp32',
-            'data': 'synthetic (headless C++ Cube-scene producers, random rotations)',
+            'data': ('synthetic (headless C++ Cube-scene producers, one fixed rotation: --dump-outputs)'
+                     if args.dump_outputs else 'synthetic (headless C++ Cube-scene producers, random rotations)'),
             'config': {
                 'model': f'cube-scene-{res_w}x{res_h}-' + args.mode + (' + dcgan-disc' if model is not None else ''),
                 'global_batch': args.batch * world,
@@ -750,8 +830,11 @@ def main(argv=None):
             'ring_t0': win.get('ring_t0'),
             'ring_t1': win.get('ring_t1'),
             'consumer_wait_ms_per_batch': _r(win.get('consumer_wait_ms_per_batch'), 4),
-            # ~--sustain-s more steps right after the timed ones (not part of value)
+            # --full: ~--sustain-s more steps right after the timed ones (not part of value)
             'sustained': sustained,
+            'full': args.full,
+            # --dump-outputs: {file: shape} of rank 0's last timed step
+            'dumped_outputs': dumped,
             # whole run incl. start-up (for comparison with the window)
             'run_frames_per_producer': metrics.get('frames_per_producer'),
             'cpu': cpu,

@@ -17,7 +17,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $O/smoke.log
 timeout -k 10 300 python bench.py > $O/bench_default.log 2>&1 || { tail -5 $O/bench_default.log; exit 1; }
 grep '^{' $O/bench_default.log | tee $O/bench_default.jsonl | cut -c1-200
-timeout -k 10 300 python bench.py --steps 20 --warmup 10 > $O/bench_20.log 2>&1 || { tail -5 $O/bench_20.log; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 10 > $O/bench_20.log 2>&1 || { tail -5 $O/bench_20.log; exit 1; }
 grep '^{' $O/bench_20.log | tee $O/bench_20.jsonl | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'v20':d['value'],'backlog':d['backlog_covers_window'],'sustained':d['sustained']}))"
 for v in "default:" "pre:BT_C4P_PRE=1" "default:" "pre:BT_C4P_PRE=1"; do
   name=${v%%:*}; e=${v#*:}

@@ -68,3 +68,44 @@ def test_bench_cli_fleet_and_jitter_flags():
     import os
     cpus = len(os.sched_getaffinity(0))
     assert _default_io_threads(['tcp://127.0.0.1:5000'] * 8) == min(8, max(4, cpus - 2))
+
+
+def test_bench_cli_full_and_dump_outputs(tmp_path):
+    """bench.py: --full and --dump-outputs are off by default; ensure_built
+    leaves a tree it cannot write to as built; dump_outputs
+    writes float32 .npy files that share the 64 MB budget -- a small array
+    whole, an oversized one as the same seeded sample on every call."""
+    import importlib.util
+    import numpy as np
+    import torch
+    from helpers import ROOT
+    spec = importlib.util.spec_from_file_location('bench_dump', ROOT / 'bench.py')
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    a = mod.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert not a.full and a.dump_outputs is None and a.steps == 7
+    a = mod.parse_args(['--full', '--dump-outputs', str(tmp_path / 'd')])
+    assert a.full and a.dump_outputs == str(tmp_path / 'd')
+    # a tree whose build/ cannot be created (here: its parent is a file) runs as
+    # built, and one that is not built says so instead of trying to compile
+    real_root = mod.ROOT
+    (tmp_path / 'ro').write_text('')
+    mod.ROOT = tmp_path / 'ro'
+    mod.ensure_built()
+    mod.PKG = tmp_path
+    with pytest.raises(RuntimeError, match='not built'):
+        mod.ensure_built()
+    mod.ROOT, mod.PKG = real_root, real_root / 'pytorch-blender_amd'
+    mod.DUMP_BUDGET_BYTES = 4 * 1000          # 1000 float32 elements in all
+    big = torch.arange(5000, dtype=torch.float64).reshape(50, 100)
+    outs = {'image': big.to(torch.uint8), 'loss': torch.tensor([0.25], dtype=torch.bfloat16)}
+    w1 = mod.dump_outputs(tmp_path / 'a', outs)
+    w2 = mod.dump_outputs(tmp_path / 'b', outs)
+    assert w1 == w2 == {'loss.npy': [1], 'image.npy': [999]}
+    img, loss = np.load(tmp_path / 'a' / 'image.npy'), np.load(tmp_path / 'a' / 'loss.npy')
+    assert img.dtype == np.float32 and loss.dtype == np.float32 and loss.tolist() == [0.25]
+    assert np.array_equal(img, np.load(tmp_path / 'b' / 'image.npy'))
+    assert set(img.tolist()) <= set(big.to(torch.uint8).reshape(-1).tolist())
+    small = mod.dump_outputs(tmp_path / 'c', {'image': big[:5]}, rank=1, world=2)
+    assert small == {'image.rank1.npy': [5, 100]}
+    assert np.array_equal(np.load(tmp_path / 'c' / 'image.rank1.npy'), big[:5].numpy().astype(np.float32))
