@@ -168,7 +168,7 @@ class Discriminator(nn.Module):
         if ok:
             # adaptive stack: the last BN's apply runs in the head's pooling (BnActLazy)
             z, link, lazy = self._run_bf16(x, body, mfma, want_link=True, lut=lut, want_lazy=True,
-                                           lazy_tail=adaptive and self.lazy_head_bn)
+                                           lazy_tail=adaptive and self.lazy_head_bn, round_once=True)
             if adaptive or tuple(z.shape[2:]) == pool:
                 if not z.is_contiguous(memory_format=torch.channels_last):
                     if lazy is not None:
@@ -178,9 +178,9 @@ class Discriminator(nn.Module):
                 if probs == 'logits':
                     return loss, logits
                 return loss, (torch.sigmoid(logits) if probs else None)
-            out = self._run_bf16(z, layers[len(body):], mfma)
+            out = self._run_bf16(z, layers[len(body):], mfma, round_once=True)
         else:
-            out = self._run_bf16(x, layers, mfma)
+            out = self._run_bf16(x, layers, mfma, round_once=True)
         out = out.reshape(-1).float()
         tgt = target if isinstance(target, torch.Tensor) else torch.full_like(out, float(target))
         return F.binary_cross_entropy(out, tgt), out
@@ -204,7 +204,8 @@ class Discriminator(nn.Module):
                 and isinstance(nxt, ops.BatchNormLeakyReLU2d) and ops.bn_acc_supported(m.out_channels)
                 and nxt.fused_with_stats(x.new_empty((1, m.out_channels, 1, 1), dtype=torch.bfloat16)))
 
-    def _run_bf16(self, x, layers, mfma, want_link=False, lut=None, lazy_tail=False, want_lazy=False):
+    def _run_bf16(self, x, layers, mfma, want_link=False, lut=None, lazy_tail=False, want_lazy=False,
+                  round_once=False):
         import torch.nn.functional as F
         from .. import ops
         convs = [m for m in layers if isinstance(m, nn.Conv2d)]
@@ -287,7 +288,18 @@ class Discriminator(nn.Module):
                     if act_next is not None:
                         raise RuntimeError('_run_bf16: a lazily applied BN feeds a layer off the MFMA path')
                     link = None
-                    x = F.conv2d(x, w16, None, m.stride, m.padding, m.dilation, m.groups)
+                    if round_once and mfma and x.is_cuda and x.dtype == torch.bfloat16:
+                        # the training step (bce_bf16): a layer off the MFMA path keeps the MFMA
+                        # layers' contract -- full-precision accumulation, ONE round-to-nearest to
+                        # bf16.  The library's bf16 convolution does not give that on gfx950: the
+                        # 3-channel first layer's output came out truncated (0.28 % low in the
+                        # mean), 5-14 % error in every gradient of the step (docs/STEP_ORACLE.md,
+                        # rgb-bf16).  forward_bf16 keeps the library's bf16 call: it is documented
+                        # as the autocast path
+                        x = F.conv2d(x.float(), w16.float(), None, m.stride, m.padding, m.dilation,
+                                     m.groups).to(torch.bfloat16)
+                    else:
+                        x = F.conv2d(x, w16, None, m.stride, m.padding, m.dilation, m.groups)
             elif stats is not None and isinstance(m, ops.BatchNormLeakyReLU2d):
                 link = ops.BnLink() if torch.is_grad_enabled() else None
                 acc_bf16 = isinstance(stats, ops.BnAccumulator) and x.dtype == torch.bfloat16
