@@ -7,6 +7,7 @@
 #include <unistd.h>
 
 #include "../codec/tiledelta.h"
+#include "../common/planar_alpha.h"
 #include "../common/trace.h"
 
 #include <algorithm>
@@ -586,9 +587,18 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     guard.armed = true;   // claimed: every exit but the hand-over to cur_ gives it back
     it.src = it.seg->base() + off;
     if (dev_base) it.dsrc = dev_base + off;
-    if (d.items.size() >= 9 && d.items[8]->kind == codec::Value::TUPLE) {
+    const codec::Value* tag = has_codec ? d.items[8].get() : nullptr;
+    if (tag && tag->items.size() == 1 && tag->items[0]->kind == codec::Value::STR && tag->items[0]->s == planar::kName) {
+      // 9th element ('rgb_a',): packed RGB, then the alpha plane.  The whole
+      // H*W*4 frame must lie inside this slot: the kernel reads the RGB part
+      // in place and materialize() the alpha plane behind it
+      const size_t slot_lo = it.seg->slot_offset(it.slot);
+      if (c != 4 || size_t(off) < slot_lo || !planar::rgb_a_valid(h, w, off, slot_lo + it.seg->slot_bytes()))
+        return bad("_btshm rgb_a frame out of range");
+      it.planar = true;
+    } else if (tag) {
       // 9th element (codec, key segment, key generation): key-frame delta
-      const codec::Value& cd = *d.items[8];
+      const codec::Value& cd = *tag;
       if (cd.items.size() < 3 || cd.items[0]->kind != codec::Value::STR || cd.items[0]->s != tiledelta::kName ||
           cd.items[1]->kind != codec::Value::STR)
         return bad("unknown _btshm codec");
@@ -733,6 +743,11 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     if (it.tiled) {
       stats_.image_bytes += 4 * (size_t(it.ntiles) + 1) + size_t(it.ntiles) * tiledelta::tile_bytes(c);
       stats_.tiled_frames++;
+    } else if (it.planar) {
+      // only the RGB part crosses the link when the frame is read in place;
+      // materialize() adds the alpha plane's bytes if it has to rebuild it
+      stats_.image_bytes += size_t(h) * w * 3;
+      stats_.planar_frames++;
     } else {
       stats_.image_bytes += img_bytes_;
     }
@@ -778,7 +793,27 @@ const void* StreamLoader::decoded_key(KeyFrame& kf, bool flip, size_t out_img_by
   return d;
 }
 
-void StreamLoader::materialize(Item& it) {
+bool StreamLoader::reads_rgb_only() const {
+  if (!cfg_.planar_alpha || !cfg_.direct || cfg_.color_matrix || passthrough_) return false;
+  for (int k = 0; k < cfg_.cout; ++k)
+    if (cfg_.cmap[k] == 3) return false;
+  return true;
+}
+
+void StreamLoader::materialize(Item& it, bool keep_planar) {
+  if (it.planar && !keep_planar) {
+    // the batch cannot read packed RGB in place (copy path, alpha needed,
+    // colour kernel): back to interleaved RGBA, as tiled frames are rebuilt
+    const size_t npix = size_t(H_) * W_;
+    it.expanded.resize(img_bytes_);
+    planar::interleave_rgb_a(it.expanded.data(), it.src, it.src + npix * 3, npix);
+    it.src = it.expanded.data();
+    it.dsrc = nullptr;
+    it.planar = false;
+    std::lock_guard<std::mutex> lk(mu_);
+    stats_.image_bytes += npix;
+    return;
+  }
   if (!it.tiled) return;
   it.expanded.resize(img_bytes_);
   tiledelta::expand(it.src, it.key_host, H_, W_, C_, it.expanded.data());
@@ -799,6 +834,10 @@ StreamLoader::MappedSegment& StreamLoader::segment(const std::string& name) {
   check(hipHostRegister(ms.seg->base(), ms.seg->size(), hipHostRegisterMapped), "hipHostRegister(shm)");
   if (hipHostGetDevicePointer(reinterpret_cast<void**>(&ms.dev_base), ms.seg->base(), 0) != hipSuccess)
     ms.dev_base = nullptr;
+  // tell the producer how this loader reads its frames (sticky, shmring.h):
+  // RGB only and in place -> it may keep alpha out of the bytes the kernel
+  // pulls over the link; anything else needs interleaved pixels
+  ms.seg->add_hint(reads_rgb_only() && ms.dev_base ? shm::kWantPlanarAlpha : shm::kNeedInterleaved);
   {
     std::lock_guard<std::mutex> lk(mu_);
     seg_list_.push_back(ms.seg.get());   // ring occupancy in stats()
@@ -921,8 +960,11 @@ void StreamLoader::launch() {
   // are rebuilt on the host
   pb.tiled = direct && !cfg_.color_matrix &&
              std::all_of(cur_.begin(), cur_.end(), [&](const Item& it) { return it.tiled && aligned(it); });
+  // rgb_a frames are read in place (Cin = 3) by an RGB-only direct decode;
+  // anywhere else they are re-interleaved on the host
+  const bool planar_in_place = direct && reads_rgb_only();
   if (!pb.tiled)
-    for (auto& it : cur_) materialize(it);
+    for (auto& it : cur_) materialize(it, planar_in_place && aligned(it));
   // mixed batches stay on the direct path: a frame the kernel cannot read in
   // place (heap-received: dry pool, rebuilt on the host, unaligned) is copied
   // into a free pinned slot here, and the rest are still read where they lie
@@ -939,6 +981,8 @@ void StreamLoader::launch() {
       stats_.staged_frames++;
     }
   pb.direct = direct && std::all_of(cur_.begin(), cur_.end(), aligned);
+  if (!pb.direct)
+    for (auto& it : cur_) materialize(it);   // the copy path moves whole interleaved frames
   pb.items = std::move(cur_);
   cur_.clear();
   pending_images_ += int(pb.items.size());
@@ -1133,6 +1177,10 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     std::memcpy(cp.flip_bits, flips, sizeof(flips));
     e = color4x4(cp, stream_);
   } else {
+    // rgb_a frames (direct path only: launch() re-interleaved the others) are
+    // read in place as packed RGB, Cin = 3
+    int nplanar = 0;
+    for (const Item* it : all) nplanar += it->planar ? 1 : 0;
     DecodeParams dp;
     dp.src = stage;
     dp.dst = group.front().dst;
@@ -1147,13 +1195,36 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
         for (size_t k = 0; k < b.items.size(); ++k) dp.dsts[i++] = static_cast<uint8_t*>(b.dst) + k * out_img_bytes;
     }
     dp.lut = d_lut_;
-    dp.B = total, dp.H = H_, dp.W = W_, dp.Cin = C_, dp.Cout = cfg_.cout;
+    dp.B = total, dp.H = H_, dp.W = W_, dp.Cin = nplanar == total ? 3 : C_, dp.Cout = cfg_.cout;
     std::memcpy(dp.cmap, cfg_.cmap, sizeof(dp.cmap));
     dp.flip_all = cfg_.flip_all;
     std::memcpy(dp.flip_bits, flips, sizeof(flips));
     dp.out_dtype = cfg_.out_dtype;
     dp.layout = cfg_.layout;
-    if (group.front().tiled) {
+    if (nplanar > 0 && nplanar < total) {
+      // both source layouts in one group (a mixed fleet with inline
+      // producers, or the first frames before a producer saw the hint): one
+      // launch per layout, each with its own images, outputs and flip bits
+      for (int pl = 0; pl < 2 && e == hipSuccess; ++pl) {
+        DecodeParams sp = dp;
+        std::memset(sp.flip_bits, 0, sizeof(sp.flip_bits));
+        int n = 0, i = 0;
+        for (auto& b : group)
+          for (size_t k = 0; k < b.items.size(); ++k, ++i) {
+            const Item& it = *all[size_t(i)];
+            if (it.planar != (pl == 1)) continue;
+            sp.srcs[n] = it.dsrc;
+            sp.dsts[n] = static_cast<uint8_t*>(b.dst) + k * out_img_bytes;
+            if (it.flip) sp.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
+            ++n;
+          }
+        sp.B = sp.nsrcs = sp.ndsts = n;
+        sp.Cin = pl == 1 ? 3 : C_;
+        e = decode(sp, stream_);
+      }
+      // (stats_.launches counts launch groups: this one stays one coalesced
+      // launch for the batches in it, run as two kernels)
+    } else if (group.front().tiled) {
       TileParams tp;
       tp.out_img_bytes = int64_t(out_img_bytes);
       tp.payload_off = int64_t(tiledelta::payload_offset(H_, W_));

@@ -124,6 +124,11 @@ struct LoaderConfig {
   // loader thread held up the consumer's graph launches (~0.2 ms per step of
   // the disc consumer).  false: the GPU-side waits of round 1.
   bool host_sync = true;
+  // Ring hint (shmring.h): true = a loader that reads RGB only, in place
+  // (direct path, no alpha in the channel map, no colour kernel) asks its
+  // producers for rgb_a frames and leaves the alpha plane in host memory;
+  // false = always ask for interleaved frames.
+  bool planar_alpha = true;
   // decode parameters (src/dst/B/H/W/Cin filled per batch)
   int cout = 3;
   int cmap[4] = {0, 1, 2, 3};
@@ -196,6 +201,7 @@ struct LoaderStats {
   uint64_t launches = 0;                   // decode kernel launches (< batches when coalesced)
   uint64_t image_bytes = 0;                // image bytes that crossed host -> device
   uint64_t tiled_frames = 0;               // key-frame delta frames (tiledelta.h)
+  uint64_t planar_frames = 0;              // shm frames that arrived as rgb_a (planar_alpha.h)
   double h2d_issue_ms = 0;
   // GPU time of every kTimedEvery-th launch (timing events around its H2D
   // copies + decode kernel): per-image device cost without timing every launch
@@ -250,12 +256,18 @@ class StreamLoader {
     int ntiles = 0;
     KeyFrame* key = nullptr;
     const uint8_t* key_host = nullptr;
+    // rgb_a slot (csrc/common/planar_alpha.h): `src`/`dsrc` point at H*W*3
+    // bytes of packed RGB, the alpha plane follows; read in place with Cin = 3
+    bool planar = false;
     std::vector<uint8_t> expanded;     // copy path: the frame rebuilt on the host
     BufPtr staged;                     // pinned slot a heap-received image was copied into (direct path)
     float jit[4] = {1.f, 1.f, 1.f, 0.f};   // colour-jitter factors (LoaderConfig::jitter)
     BatchMeta meta;
   };
-  void materialize(Item& it);
+  // rebuild on the host what the batch cannot read in place: a key-frame
+  // delta, and (unless keep_planar) an rgb_a frame back to interleaved RGBA
+  void materialize(Item& it, bool keep_planar = false);
+  bool reads_rgb_only() const;        // this loader's decode never needs a frame's alpha or interleaving
   struct Posted {
     void* dst;
     hipEvent_t ready;

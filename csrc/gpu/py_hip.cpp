@@ -1077,9 +1077,11 @@ PYBIND11_MODULE(_hip, m) {
                        int staging_depth, bool skip_bad, int cout, std::vector<int> cmap, int flip_all,
                        int out_dtype, int layout, std::vector<float> lut, std::vector<float> matrix,
                        std::vector<float> bias, bool direct, int launch_depth, int copy_streams, bool host_sync,
-                       std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed) {
+                       std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed,
+                       bool planar_alpha) {
              LoaderConfig c;
              c.direct = direct;
+             c.planar_alpha = planar_alpha;
              c.host_sync = host_sync;
              c.copy_streams = copy_streams;
              c.launch_depth = launch_depth;
@@ -1122,7 +1124,7 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"), py::arg("lut"), py::arg("matrix"),
            py::arg("bias"), py::arg("direct") = true, py::arg("launch_depth") = 2,
            py::arg("copy_streams") = 2, py::arg("host_sync") = true, py::arg("matrices") = std::vector<float>(),
-           py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0)
+           py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0, py::arg("planar_alpha") = true)
       .def("start", &StreamLoader::start)
       .def("wait_shape",
            [](StreamLoader& l, long timeout_ms) -> py::object {
@@ -1197,6 +1199,7 @@ PYBIND11_MODULE(_hip, m) {
         d["launches"] = s.launches;
         d["image_bytes"] = s.image_bytes;
         d["tiled_frames"] = s.tiled_frames;
+        d["planar_frames"] = s.planar_frames;
         d["timed_launches"] = s.timed_launches;
         d["timed_images"] = s.timed_images;
         d["timed_gpu_ms"] = s.timed_gpu_ms;

@@ -9,8 +9,10 @@
 
 #include "../codec/pickle_codec.h"
 #include "../codec/xform_fit.h"
+#include "../common/planar_alpha.h"
 #include "../sim/physics.h"
 #include "../sim/raster.h"
+#include "../transport/shmring.h"
 #include "../transport/zmtp.h"
 #include "pyvalue.h"
 
@@ -233,6 +235,44 @@ class NativeError(Exception):
     if (info.ndim != 1 || i >= size_t(info.shape[0])) throw py::index_error("slot index out of range");
     auto* w = reinterpret_cast<std::atomic<uint32_t>*>(static_cast<uint32_t*>(info.ptr) + i);
     return w->compare_exchange_strong(expected, desired, std::memory_order_acq_rel);
+  });
+
+  // Consumer hint word of a ring segment (shmring.h Header::hint) through a
+  // writable buffer over the whole mapping (the Python mirror's mmap): the
+  // same atomic OR / relaxed load as Segment::add_hint / hint.
+  auto ring_header = [](py::buffer seg, bool writable) {
+    auto info = seg.request(writable);
+    if (size_t(info.size * info.itemsize) < sizeof(shm::Header))
+      throw py::value_error("not a blendtorch shm segment (too small)");
+    auto* h = static_cast<shm::Header*>(info.ptr);
+    if (h->magic != shm::kMagic) throw py::value_error("not a blendtorch shm segment");
+    if (h->version != shm::kVersion)
+      throw py::value_error("shm ring header version " + std::to_string(h->version) + ", this build reads version " +
+                            std::to_string(shm::kVersion));
+    return h;
+  };
+  m.def("ring_add_hint", [ring_header](py::buffer seg, uint32_t bits) {
+    shm::Header* h = ring_header(seg, true);
+    return reinterpret_cast<std::atomic<uint32_t>*>(&h->hint)->fetch_or(bits, std::memory_order_relaxed) | bits;
+  });
+  m.def("ring_hint", [ring_header](py::buffer seg) {
+    return reinterpret_cast<std::atomic<uint32_t>*>(&ring_header(seg, false)->hint)->load(std::memory_order_relaxed);
+  });
+  m.attr("RING_VERSION") = shm::kVersion;
+  m.attr("WANT_PLANAR_ALPHA") = shm::kWantPlanarAlpha;
+  m.attr("NEED_INTERLEAVED") = shm::kNeedInterleaved;
+  // An rgb_a frame (csrc/common/planar_alpha.h) at byte offset `off` of a
+  // buffer, which ends the frame's slot at `slot_end`: the interleaved
+  // H x W x 4 array the CPU dataset path hands out.
+  m.def("interleave_rgb_a", [](py::buffer seg, int64_t off, int64_t h, int64_t w, int64_t slot_end) {
+    auto info = seg.request();
+    const uint64_t size = uint64_t(info.size * info.itemsize);
+    if (slot_end < 0 || uint64_t(slot_end) > size || !planar::rgb_a_valid(h, w, off, uint64_t(slot_end)))
+      throw py::value_error("rgb_a frame out of range");
+    py::array_t<uint8_t> out({py::ssize_t(h), py::ssize_t(w), py::ssize_t(4)});
+    const uint8_t* rgb = static_cast<const uint8_t*>(info.ptr) + off;
+    planar::interleave_rgb_a(out.mutable_data(), rgb, rgb + size_t(h) * size_t(w) * 3, size_t(h) * size_t(w));
+    return out;
   });
 
   // ---- codec ----

@@ -15,8 +15,15 @@
 // --lease-ms N       shm ring lease (default 30000): unclaimed slots reclaimed after starving N ms
 // --shm N (render into an N-slot shared-memory ring, send descriptors only)
 // --codec tile16 (shm frames as key-frame deltas, csrc/codec/tiledelta.h)
+// --shm-layout auto|interleaved|planar  (RGBA shm frames, codec none; env
+//   BLENDTORCH_SHM_LAYOUT): planar = packed RGB then the alpha plane (`rgb_a`,
+//   csrc/common/planar_alpha.h); auto (default) follows the ring's consumer
+//   hint frame by frame (shmring.h); where the layout does not apply (RGB
+//   frames, tile16, H*W*3 % 16 != 0) frames stay interleaved
 // --bench N (no sockets: render N frames into 8 rotating buffers, full vs
-// incremental (DirtyRect) rendering, and report the byte mismatches -- 0)
+// incremental (DirtyRect) rendering, and report the byte mismatches -- 0;
+// with --shm-layout planar the incremental frames are rgb_a slots, compared
+// byte for byte in HWC order against the full 4-channel render)
 //
 // Every frame it publishes, on a bound PUSH socket with SNDHWM/LINGER/
 // IMMEDIATE as btb.DataPublisher does (reference: btb/publisher.py:21-43),
@@ -42,6 +49,7 @@
 
 #include "../codec/pickle_codec.h"
 #include "../codec/tiledelta.h"
+#include "../common/planar_alpha.h"
 #include "../transport/shmring.h"
 #include "../transport/zmtp.h"
 #include "physics.h"
@@ -72,6 +80,7 @@ struct Args {
   bool verbose = false;
   int shm_slots = 0;        // >0: images go through a shared-memory ring
   std::string codec = "none";   // shm frames: none (raw HWC) | tile16 (key-frame delta, tiledelta.h)
+  std::string shm_layout = "auto";   // RGBA shm frames: auto (ring hint) | interleaved | planar (rgb_a)
   bool fixed_rotation = false;
   double rot[3] = {0, 0, 0};
   int width = 0, height = 0;   // 0: the scene's resolution (640x480)
@@ -90,7 +99,7 @@ Args parse(int argc, char** argv) {
   // BlenderLauncher(shm_slots=N) exports BLENDTORCH_SHM_SLOTS; --shm overrides
   if (const char* e = std::getenv("BLENDTORCH_SHM_SLOTS")) a.shm_slots = std::atoi(e);
   if (const char* e = std::getenv("BLENDTORCH_SHM_CODEC")) a.codec = e;   // BlenderLauncher(shm_codec=...)
-  if (const char* e = std::getenv("BLENDTORCH_SHM_CODEC")) a.codec = e;
+  if (const char* e = std::getenv("BLENDTORCH_SHM_LAYOUT")) a.shm_layout = e;
   std::vector<std::string> v;
   int start = 1;
   for (int i = 1; i < argc; ++i)
@@ -133,6 +142,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--lease-ms") a.lease_ms = std::stol(need(i)), ++i;
     else if (k == "--shm") a.shm_slots = std::stoi(need(i)), ++i;
     else if (k == "--codec") a.codec = need(i), ++i;
+    else if (k == "--shm-layout") a.shm_layout = need(i), ++i;
     else if (k == "--bench") a.bench = std::stoll(need(i)), ++i;
     else if (k == "--resolution") {
       // WxH: render size (render.resolution_x/_y); the camera's field of view is kept
@@ -154,6 +164,8 @@ Args parse(int argc, char** argv) {
   }
   if (a.mode != "rgb" && a.mode != "rgba") usage("--mode must be rgb or rgba");
   if (a.codec != "none" && a.codec != btn::tiledelta::kName) usage("--codec must be none or tile16");
+  if (a.shm_layout != "auto" && a.shm_layout != "interleaved" && a.shm_layout != "planar")
+    usage("--shm-layout must be auto, interleaved or planar");
   if (a.origin != "upper-left" && a.origin != "lower-left") usage("bad --origin");
   return a;
 }
@@ -197,9 +209,15 @@ zmtp::Frame frame_from_vector(codec::Bytes&& v) {
 // 8 rotating buffers (a ring slot's life; the full renders rotate over 8
 // buffers of their own); both timings and the number of
 // differing bytes (must be 0) are printed.
+// A slot's alpha plane in the rgb_a layout.  raster.h guarantees alpha = 255
+// everywhere, so the plane is written only when the slot last held something
+// else (and by --stamp).
+void fill_alpha_plane(uint8_t* slot, size_t npix) { std::memset(slot + npix * 3, 255, npix); }
+
 template <class Pose>
-int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose) {
+int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::Renderer* planar) {
   const size_t n = size_t(r.width()) * r.height() * r.channels();
+  const size_t npix = size_t(r.width()) * r.height();
   constexpr int kSlots = 8;
   std::vector<std::vector<uint8_t>> slots(kSlots, std::vector<uint8_t>(n));
   std::vector<sim::DirtyRect> dirty(kSlots);
@@ -216,13 +234,21 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose) {
     r.render(scene, fulls[size_t(i % kSlots)].data());
     auto t1 = std::chrono::steady_clock::now();
     uint8_t* out = slots[size_t(i % kSlots)].data();
-    r.render(scene, out, &dirty[size_t(i % kSlots)]);
+    if (planar) {
+      if (!dirty[size_t(i % kSlots)].known) fill_alpha_plane(out, npix);
+      planar->render(scene, out, &dirty[size_t(i % kSlots)]);
+    } else {
+      r.render(scene, out, &dirty[size_t(i % kSlots)]);
+    }
     auto t2 = std::chrono::steady_clock::now();
     t_full += std::chrono::duration<double, std::milli>(t1 - t0).count();
     t_inc += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    // compared (and hashed) in the frame's logical HWC byte order; a planar
+    // slot is read where it lies, so both layouts touch the same memory here
     for (size_t k = 0; k < n; ++k) {
-      mismatches += out[k] != full[k];
-      h = (h ^ out[k]) * 1099511628211ull;
+      const uint8_t v = !planar ? out[k] : ((k & 3) == 3 ? out[npix * 3 + (k >> 2)] : out[(k >> 2) * 3 + (k & 3)]);
+      mismatches += v != full[k];
+      h = (h ^ v) * 1099511628211ull;
     }
   }
   std::printf("{\"frames\": %lld, \"full_ms\": %.4f, \"incremental_ms\": %.4f, \"mismatched_bytes\": %lld, "
@@ -273,8 +299,20 @@ int main(int argc, char** argv) {
     }
   };
   const bool lower_left = a.origin == "lower-left";
-  sim::Renderer renderer(scene, C, lower_left);
-  if (a.bench > 0) return bench(a, scene, renderer, pose);
+  // one Renderer per stored layout, built when first used: the frame's own
+  // channels (interleaved), and 3 channels for the RGB part of rgb_a slots
+  std::unique_ptr<sim::Renderer> renderer_hwc, renderer_rgb;
+  auto renderer = [&]() -> sim::Renderer& {
+    if (!renderer_hwc) renderer_hwc.reset(new sim::Renderer(scene, C, lower_left));
+    return *renderer_hwc;
+  };
+  auto planar_renderer = [&]() -> sim::Renderer& {
+    if (!renderer_rgb) renderer_rgb.reset(new sim::Renderer(scene, 3, lower_left));
+    return *renderer_rgb;
+  };
+  const bool planar_ok = planar::supported(H, W, C);
+  if (a.bench > 0)
+    return bench(a, scene, renderer(), pose, a.shm_layout == "planar" && planar_ok ? &planar_renderer() : nullptr);
 
   auto sock = zmtp::Context::global().socket(zmtp::PUSH);
   sock->setsockopt(zmtp::SNDHWM, a.sndhwm);
@@ -295,7 +333,7 @@ int main(int argc, char** argv) {
       if (tiled) {
         key_seg.reset(shm::Segment::create(name + "-key", 1, raw));
         const int k = key_seg->acquire(0);
-        std::memcpy(key_seg->slot(uint32_t(k)), renderer.background().data(), raw);
+        std::memcpy(key_seg->slot(uint32_t(k)), renderer().background().data(), raw);
         key_seg->publish(uint32_t(k));   // stays published: consumers only read it
       }
     } catch (const std::exception& e) {
@@ -311,6 +349,11 @@ int main(int argc, char** argv) {
   const char* full_env = std::getenv("BLENDTORCH_FULL_RENDER");
   const bool incremental = !(full_env && std::atoi(full_env) != 0);
   std::vector<sim::DirtyRect> slot_dirty(seg ? size_t(a.shm_slots) : 0);
+  // which layout each slot last held: a slot whose layout changes holds
+  // unknown content (full background copy; alpha plane filled for rgb_a)
+  enum SlotLayout : uint8_t { kUnknown = 0, kInterleaved = 1, kPlanar = 2 };
+  std::vector<uint8_t> slot_layout(seg ? size_t(a.shm_slots) : 0, uint8_t(kUnknown));
+  const size_t npix = size_t(W) * H;
   const auto t_start = std::chrono::steady_clock::now();
   auto next_due = t_start;
   long long published = 0;
@@ -325,6 +368,11 @@ int main(int argc, char** argv) {
       slot = seg->acquire(-1, &g_stop, a.lease_ms);   // blocks while every slot is with a consumer
       if (slot < 0) break;
     }
+    // this frame's layout: rgb_a when the ring's consumers all read RGB in
+    // place (the hint is re-read every frame: consumers come and go)
+    bool planar = false;
+    if (seg && !tiled && planar_ok && a.shm_layout != "interleaved")
+      planar = a.shm_layout == "planar" || (seg->hint() & 3u) == shm::kWantPlanarAlpha;
     uint32_t gen = 0;
     codec::Writer w(4, g_pool.take());
     w.begin_dict();
@@ -374,6 +422,10 @@ int main(int argc, char** argv) {
         w.str(key_seg->name());
         w.integer(int64_t(key_seg->state(0) >> 2));
         w.end_tuple();
+      } else if (planar) {   // 9th element: (layout,)
+        w.begin_tuple();
+        w.str(planar::kName);
+        w.end_tuple();
       }
       w.end_tuple();
     }
@@ -385,15 +437,35 @@ int main(int argc, char** argv) {
     sim::DirtyRect* dirty = tiled ? &tiled_dirty : (seg && incremental ? &slot_dirty[size_t(slot)] : nullptr);
     uint8_t* const slot_bytes = pixels;
     if (tiled) pixels = tiled_frame.data();
-    renderer.render(scene, pixels, dirty);
+    if (seg && !tiled) {
+      uint8_t& held = slot_layout[size_t(slot)];
+      const uint8_t now = planar ? kPlanar : kInterleaved;
+      if (held != now) {
+        slot_dirty[size_t(slot)] = sim::DirtyRect();   // unknown content: full background copy
+        if (planar) fill_alpha_plane(pixels, npix);
+        held = now;
+      }
+    }
+    (planar ? planar_renderer() : renderer()).render(scene, pixels, dirty);
     if (a.stamp) {
       // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
       // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
       uint8_t st[16] = {'B', 'T', uint8_t(a.btid & 0xff), uint8_t((a.btid >> 8) & 0xff), 0, 0, 0, 0};
       const uint64_t q = uint64_t(published);
       std::memcpy(st + 8, &q, 8);
-      std::memcpy(pixels, st, sizeof(st));
-      if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+      if (planar) {
+        // the same 16 logical HWC bytes: pixels 0..3, their alpha (bytes 3, 7,
+        // 11, 15) in the alpha plane -- rewritten every frame, never restored
+        for (int p = 0; p < 4; ++p) {
+          std::memcpy(pixels + 3 * p, st + 4 * p, 3);
+          pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
+          const int row = p / W, col = p % W;   // stored row / column of pixel p
+          if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
+        }
+      } else {
+        std::memcpy(pixels, st, sizeof(st));
+        if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+      }
     }
     if (tiled) {
       // everything outside this frame's dirty rectangle is background

@@ -350,11 +350,15 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
           const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
                              uint32_t(shadow_rgb_[2]) << 16 | 0xff000000u;
           for (int x = a; x <= b; ++x) std::memcpy(r + size_t(x) * 4, &v, 4);
-        } else {
-          for (int x = a; x <= b; ++x) {
-            uint8_t* p = r + size_t(x) * C;
-            p[0] = shadow_rgb_[0], p[1] = shadow_rgb_[1], p[2] = shadow_rgb_[2];
-          }
+        } else if (a <= b) {
+          // packed RGB: one 32-bit store per pixel as well -- its 4th byte
+          // lands on the next pixel's red, which that pixel's store rewrites;
+          // the span's last pixel is written as 3 bytes
+          const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
+                             uint32_t(shadow_rgb_[2]) << 16 | uint32_t(shadow_rgb_[0]) << 24;
+          for (int x = a; x < b; ++x) std::memcpy(r + size_t(x) * 3, &v, 4);
+          uint8_t* p = r + size_t(b) * 3;
+          p[0] = shadow_rgb_[0], p[1] = shadow_rgb_[1], p[2] = shadow_rgb_[2];
         }
         return;
       }
@@ -474,7 +478,10 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
                   std::memcpy(p + size_t(k) * 4, &v, 4);
                 }
               } else if (gray) {
-                for (int k = 0; k < n; ++k, p += C) p[0] = p[1] = p[2] = T.v[i0[k]];
+                // packed RGB, as the shadow spans: 32-bit stores whose 4th
+                // byte the next pixel rewrites, the chunk's last pixel as 3 bytes
+                for (int k = 0; k + 1 < n; ++k, p += 3) std::memcpy(p, &T.gray4[i0[k]], 4);
+                p[0] = p[1] = p[2] = T.v[i0[n - 1]];
               } else {
                 for (int k = 0; k < n; ++k, p += C) p[0] = T.v[i0[k]], p[1] = T.v[i1[k]], p[2] = T.v[i2[k]];
               }

@@ -51,10 +51,12 @@ Segment* Segment::create(const std::string& name, uint32_t nslots, size_t slot_b
   s->size_ = size;
   s->owner_ = true;
   s->hdr_ = reinterpret_cast<Header*>(p);
-  s->hdr_->version = 1;
+  s->hdr_->version = kVersion;
   s->hdr_->nslots = nslots;
   s->hdr_->slot_bytes = slot_bytes;
   s->hdr_->data_offset = data_off;
+  s->hdr_->hint = 0;
+  s->hdr_->reserved = 0;
   for (uint32_t i = 0; i < nslots; ++i) new (&s->states()[i]) std::atomic<uint32_t>(FREE);
   std::atomic_thread_fence(std::memory_order_release);
   s->hdr_->magic = kMagic;
@@ -84,6 +86,12 @@ Segment* Segment::open(const std::string& name) {
   if (s->hdr_->magic != kMagic || s->hdr_->data_offset + s->hdr_->slot_bytes * s->hdr_->nslots > s->size_) {
     delete s;
     throw std::runtime_error("shm: " + path + " is not a blendtorch segment");
+  }
+  if (s->hdr_->version != kVersion) {
+    const uint32_t v = s->hdr_->version;
+    delete s;
+    throw std::runtime_error("shm: " + path + " has ring header version " + std::to_string(v) +
+                             ", this build reads version " + std::to_string(kVersion));
   }
   return s;
 }
@@ -184,6 +192,14 @@ uint32_t Segment::count(SlotState st) const {
 uint32_t Segment::state(uint32_t i) const { return states()[i].load(std::memory_order_acquire); }
 
 uint32_t Segment::free_count() const { return count(FREE); }
+
+void Segment::add_hint(uint32_t bits) {
+  reinterpret_cast<std::atomic<uint32_t>*>(&hdr_->hint)->fetch_or(bits, std::memory_order_relaxed);
+}
+
+uint32_t Segment::hint() const {
+  return reinterpret_cast<const std::atomic<uint32_t>*>(&hdr_->hint)->load(std::memory_order_relaxed);
+}
 
 }  // namespace shm
 }  // namespace btn

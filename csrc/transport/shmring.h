@@ -11,6 +11,17 @@
 // removes both kernel socket copies of every frame.
 //
 // Layout: [Header | word[nslots] (uint32) | pad to 4 KiB | slot 0 | slot 1 ...]
+// Header (version 2, 40 bytes): u64 magic, u32 version, u32 nslots, u64
+// slot_bytes, u64 data_offset, u32 hint, u32 reserved.  `hint` is written by
+// consumers and read by the producer once per frame: sticky OR-ed bits
+// (kWantPlanarAlpha: a consumer reads RGB only, in place; kNeedInterleaved: a
+// consumer needs interleaved pixels).  Bits are never cleared -- no reference
+// counts a dead consumer could leave wrong -- so a ring that ever saw
+// kNeedInterleaved stays interleaved.  A producer of RGBA frames that sees
+// kWantPlanarAlpha alone stores them as `rgb_a` (csrc/common/planar_alpha.h:
+// H*W*3 bytes of packed RGB, then the H*W alpha plane; descriptor element 9 =
+// ('rgb_a',)), and such a consumer reads only the first three quarters of
+// the slot.
 // Slot word = generation << 2 | state.  States: FREE (0) -> WRITING (1,
 // producer) -> PUBLISHED (2, generation bumped) -> HELD (3, a consumer took
 // the descriptor: CAS on the exact published word) -> FREE (consumer, after
@@ -38,6 +49,10 @@ namespace shm {
 constexpr uint64_t kMagic = 0x6d68735f7462746eull;   // "ntbt_shm"
 enum SlotState : uint32_t { FREE = 0, WRITING = 1, PUBLISHED = 2, HELD = 3 };
 constexpr long kHeldLeaseFactor = 20;
+constexpr uint32_t kVersion = 2;
+// consumer hint bits (Header::hint)
+constexpr uint32_t kWantPlanarAlpha = 1;
+constexpr uint32_t kNeedInterleaved = 2;
 
 struct Header {
   uint64_t magic;
@@ -45,7 +60,10 @@ struct Header {
   uint32_t nslots;
   uint64_t slot_bytes;
   uint64_t data_offset;
+  uint32_t hint;
+  uint32_t reserved;
 };
+static_assert(sizeof(Header) == 40, "ring header layout is shared with blendtorch/transport/shm.py");
 
 class Segment {
  public:
@@ -78,6 +96,9 @@ class Segment {
   uint32_t state(uint32_t i) const;
   uint32_t free_count() const;
   uint64_t reclaimed() const { return reclaimed_; }
+  // Consumer hint: add_hint ORs bits in (atomic, sticky); hint reads them (relaxed).
+  void add_hint(uint32_t bits);
+  uint32_t hint() const;
 
  private:
   Segment() = default;

@@ -90,6 +90,13 @@ class DeviceLoader:
         loader's pinned receive slots) the decode kernel reads them over PCIe
         itself -- one fused pass, no staging copy; otherwise the frames are
         DMA'd into a device staging ring first.  ``'copy'``: always DMA.
+    shm_alpha: str
+        ``'auto'`` (default): a loader that reads RGB only and in place
+        (direct path, no alpha in the channel map, no colour kernel) asks the
+        producers' shared-memory rings for ``rgb_a`` frames -- packed RGB
+        followed by the alpha plane -- and its kernel reads only the first
+        three quarters of each RGBA slot over PCIe (``planar_frames`` in
+        :attr:`stats`).  ``'interleaved'``: always ask for interleaved frames.
     launch_depth: int
         Direct-path decode launches the loader keeps queued on its stream.
         Batches completing while that many are in flight wait and go out
@@ -129,10 +136,14 @@ class DeviceLoader:
                  rcvhwm: int = 10, prefetch: int = 4, io_threads: Optional[int] = None, image_key: str = 'image',
                  skip_bad: bool = False, meta_to_device: bool = False, staging_depth: int = 3, h2d: str = 'auto',
                  launch_depth: int = 2, log_every: Optional[float] = None, copy_streams: int = 2,
-                 defer_post: bool = False, host_sync: Optional[bool] = None, reuse_buffers: bool = False):
+                 defer_post: bool = False, host_sync: Optional[bool] = None, reuse_buffers: bool = False,
+                 shm_alpha: str = 'auto'):
         if h2d not in ('auto', 'copy'):
             raise ValueError("h2d must be 'auto' or 'copy'")
+        if shm_alpha not in ('auto', 'interleaved'):
+            raise ValueError("shm_alpha must be 'auto' or 'interleaved'")
         self.h2d = h2d
+        self.shm_alpha = shm_alpha
         self.launch_depth = int(launch_depth)
         self.copy_streams = max(1, min(4, int(copy_streams)))
         if isinstance(addresses, str):
@@ -228,7 +239,8 @@ class DeviceLoader:
             self.addresses, self.batch_size, self.image_key, self.rcvhwm, self.io_threads, self.device.index,
             max_batches, 0, 0, self.staging_depth, self.skip_bad, cfg.cout, list(cfg.cmap) + [0] * (4 - len(cfg.cmap)),
             int(cfg.flip), ops.OUT_DTYPES[cfg.dtype], ops.LAYOUTS[cfg.layout], lut, matrix, bias,
-            self.h2d == 'auto', self.launch_depth, self.copy_streams, self.host_sync, matrices, jitter, seed)
+            self.h2d == 'auto', self.launch_depth, self.copy_streams, self.host_sync, matrices, jitter, seed,
+            self.shm_alpha == 'auto')
 
     def _post(self, loader, stream):
         shape = self.decode.out_shape(self.batch_size, *self.shape[:2])
@@ -296,6 +308,7 @@ class DeviceLoader:
             'images_per_launch': s['frames'] / s['launches'] if s['launches'] else None,
             'direct_batches': s['direct_batches'],
             'staged_frames': s.get('staged_frames', 0),
+            'planar_frames': s.get('planar_frames', 0),
             'consumer_wait_s': self._wait_s,
             'bad': s['bad'], 'shm_stale': s['shm_stale'], 'shm_torn': s['shm_torn'],
             'pool_fallbacks': s['pool_fallbacks'],

@@ -4,15 +4,23 @@ Producers on the consumer's host may place image payloads in a POSIX
 shared-memory ring and send only a descriptor ``'_btshm': (segment, slot,
 byte_offset, H, W, C, key, generation[, codec])`` in the message dict; a 9th
 element ``('tile16', key_segment, key_generation)`` marks a key-frame delta
-frame (csrc/codec/tiledelta.h), which :func:`resolve` rebuilds.  The GPU loader DMAs the
+frame (csrc/codec/tiledelta.h), which :func:`resolve` rebuilds; a 9th element
+``('rgb_a',)`` marks an RGBA frame stored as H*W*3 bytes of packed RGB followed
+by its H*W alpha bytes (csrc/common/planar_alpha.h), which :func:`resolve`
+re-interleaves into the same ``H x W x 4`` array.  The GPU loader DMAs the
 slot in place; CPU consumers call :func:`resolve`, which copies the image into
 the dict under ``key`` and hands the slot back.  :class:`ShmRing` is the
 producer side for Python publishers (``btb.DataPublisher(shm_slots=N)``).
 
-Segment layout (shared with C++): header {u64 magic, u32 version, u32 nslots,
-u64 slot_bytes, u64 data_offset}, u32 word per slot (generation << 2 |
-state; states 0 free, 1 writing, 2 published, 3 held), slots at data_offset
-(4 KiB aligned).  Descriptors carry the generation: a consumer claims the slot
+Segment layout (shared with C++): header (version 2) {u64 magic, u32 version,
+u32 nslots, u64 slot_bytes, u64 data_offset, u32 hint, u32 reserved}, u32 word
+per slot (generation << 2 | state; states 0 free, 1 writing, 2 published,
+3 held), slots at data_offset (4 KiB aligned).  ``hint`` holds sticky, OR-ed
+consumer bits (:func:`add_hint` / :func:`hint`): ``WANT_PLANAR_ALPHA`` -- a
+consumer reads RGB only, in place -- and ``NEED_INTERLEAVED``; a native
+producer stores RGBA frames as ``rgb_a`` while it sees the first bit alone.
+Bits are never cleared, so a consumer that dies leaves nothing wrong behind,
+and a ring that ever saw ``NEED_INTERLEAVED`` stays interleaved.  Descriptors carry the generation: a consumer claims the slot
 (CAS (gen, published) -> (gen, held)), copies, and hands it back (CAS (gen,
 held) -> (gen, free)).  A producer starved for its lease reclaims only
 published (unclaimed) slots, so a paused consumer never has a frame taken
@@ -29,7 +37,10 @@ import time
 import numpy as np
 
 MAGIC = 0x6d68735f7462746e
-_HDR = struct.Struct('<QIIQQ')
+VERSION = 2
+_HDR = struct.Struct('<QIIQQII')
+_HINT_WORD = 8            # index of the hint among the header's u32 words
+WANT_PLANAR_ALPHA, NEED_INTERLEAVED = 1, 2    # csrc/transport/shmring.h hint bits
 FREE, WRITING, PUBLISHED, HELD = 0, 1, 2, 3
 HELD_LEASE_FACTOR = 20    # csrc/transport/shmring.h kHeldLeaseFactor
 KEY = '_btshm'
@@ -38,6 +49,10 @@ try:   # atomic slot words (CPython build of the native module; absent inside Bl
     from .._native import slot_cas as _native_cas
 except ImportError:  # pragma: no cover - exercised only without the native build
     _native_cas = None
+try:
+    from .._native import interleave_rgb_a as _native_interleave
+except ImportError:  # pragma: no cover
+    _native_interleave = None
 
 
 def _libatomic_cas():
@@ -99,9 +114,12 @@ class _Segment:
         self.fd = fd
         self.mm = mm
         self.owner = owner
-        magic, version, nslots, slot_bytes, data_offset = _HDR.unpack_from(mm, 0)
+        magic, version, nslots, slot_bytes, data_offset, _, _ = _HDR.unpack_from(mm, 0)
         if magic != MAGIC and not owner:
             raise ValueError(f'{name} is not a blendtorch shm segment')
+        if version != VERSION and not owner:
+            raise ValueError(f'{name} has ring header version {version}, this build reads version {VERSION}')
+        self._hdr_words = np.frombuffer(mm, dtype=np.uint32, count=_HDR.size // 4, offset=0)
         self.nslots, self.slot_bytes, self.data_offset = nslots, slot_bytes, data_offset
         self.states = np.frombuffer(mm, dtype=np.uint32, count=nslots, offset=_HDR.size)
         self.ino = os.fstat(fd).st_ino
@@ -110,8 +128,20 @@ class _Segment:
         off = self.data_offset + i * self.slot_bytes
         return np.frombuffer(self.mm, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)
 
+    def add_hint(self, bits):
+        """OR ``bits`` into the ring's consumer hint (atomic, sticky); returns the new value."""
+        bits = int(bits) & 0xFFFFFFFF
+        while True:
+            cur = int(self._hdr_words[_HINT_WORD])
+            if cur | bits == cur or _cas(self._hdr_words, _HINT_WORD, cur, cur | bits):
+                return cur | bits
+
+    def hint(self):
+        return int(self._hdr_words[_HINT_WORD])
+
     def close(self):
         self.states = None
+        self._hdr_words = None
         try:
             self.mm.close()
         except BufferError:  # numpy views still alive; the mapping dies with them
@@ -185,6 +215,33 @@ def _expand_tiled(seg, off, h, w, c, codec):
     return img
 
 
+def add_hint(name, bits):
+    """OR ``bits`` (``WANT_PLANAR_ALPHA`` / ``NEED_INTERLEAVED``) into the
+    consumer hint of ring ``name``; returns the new value."""
+    return _open(name).add_hint(bits)
+
+
+def hint(name):
+    """The consumer hint bits of ring ``name``."""
+    return _open(name).hint()
+
+
+def _interleave_rgb_a(seg, slot, off, h, w, c):
+    """An ``rgb_a`` slot (packed RGB, then the alpha plane) as the interleaved
+    H x W x 4 frame (csrc/common/planar_alpha.h)."""
+    slot_lo = seg.data_offset + slot * seg.slot_bytes
+    slot_end = slot_lo + seg.slot_bytes
+    n = h * w
+    if c != 4 or h <= 0 or w <= 0 or (n * 3) % 16 or off < slot_lo or off + n * 4 > slot_end or slot_end > len(seg.mm):
+        raise ValueError(f'rgb_a frame out of range in {seg.name}')
+    if _native_interleave is not None:
+        return _native_interleave(seg.mm, off, h, w, slot_end)
+    img = np.empty((n, 4), np.uint8)
+    img[:, :3] = np.frombuffer(seg.mm, dtype=np.uint8, count=n * 3, offset=off).reshape(n, 3)
+    img[:, 3] = np.frombuffer(seg.mm, dtype=np.uint8, count=n, offset=off + n * 3)
+    return img
+
+
 def release(desc):
     """Hand a descriptor's slot back without reading it (dropped messages)."""
     name, slot, off, h, w, c, key, gen = desc[:8]
@@ -221,7 +278,9 @@ def resolve(obj, strict=False):
             raise TornFrame(f'shm slot {name}:{slot} was reclaimed before it was read')
         return None
     try:
-        if len(desc) > 8 and desc[8]:
+        if len(desc) > 8 and desc[8] and desc[8][0] == 'rgb_a':
+            img = _interleave_rgb_a(seg, slot, off, h, w, c)
+        elif len(desc) > 8 and desc[8]:
             img = _expand_tiled(seg, off, h, w, c, desc[8])
         else:
             n = h * w * c
@@ -257,10 +316,10 @@ class ShmRing:
             os.unlink(_path(name))
             raise
         mm = mmap.mmap(fd, size, mmap.MAP_SHARED, mmap.PROT_READ | mmap.PROT_WRITE)
-        _HDR.pack_into(mm, 0, 0, 1, nslots, slot_bytes, data_offset)
+        _HDR.pack_into(mm, 0, 0, VERSION, nslots, slot_bytes, data_offset, 0, 0)
         self.seg = _Segment(name, fd, mm, True)
         self.seg.states[:] = FREE
-        _HDR.pack_into(mm, 0, MAGIC, 1, nslots, slot_bytes, data_offset)
+        _HDR.pack_into(mm, 0, MAGIC, VERSION, nslots, slot_bytes, data_offset, 0, 0)
         self._next = 0
         self._published_at = {}
         self.reclaimed = 0
