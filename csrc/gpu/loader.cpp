@@ -141,6 +141,8 @@ StreamLoader::StreamLoader(const LoaderConfig& cfg) : cfg_(cfg) {
   if (cfg_.lut.size() != size_t(kTableFloats))
     throw std::invalid_argument("StreamLoader: lut must hold 4*256 or kTableFloats floats");
   if (cfg_.cout < 1 || cfg_.cout > 4) throw std::invalid_argument("StreamLoader: cout must be 1..4");
+  if (cfg_.decode_streams < 1 || cfg_.decode_streams > kMaxDecodeStreams)
+    throw std::invalid_argument("StreamLoader: decode_streams must be 1..4");
   if (cfg_.color_matrix && !cfg_.jitter && cfg_.matrices.empty() && (cfg_.matrix.size() != 16 || cfg_.bias.size() != 4))
     throw std::invalid_argument("StreamLoader: colour matrix needs 16 + 4 floats");
   if (!cfg_.matrices.empty() && cfg_.matrices.size() != size_t(cfg_.batch_size) * 20)
@@ -333,6 +335,13 @@ void StreamLoader::stop() {
   copy_streams_.clear();
   for (auto ev : copy_done_) (void)hipEventDestroy(ev);
   copy_done_.clear();
+  // launches may be in flight on every decode stream: all of them drain (and
+  // the extra ones go) before reap(true) hands their slots back
+  for (size_t k = 1; k < decode_streams_.size(); ++k) {
+    (void)hipStreamSynchronize(decode_streams_[k]);
+    (void)hipStreamDestroy(decode_streams_[k]);
+  }
+  decode_streams_.clear();
   if (stream_) {
     (void)hipStreamSynchronize(stream_);
     reap(true);                            // drop pinned refs of finished copies
@@ -990,10 +999,29 @@ void StreamLoader::launch() {
   flush_pending(false);
 }
 
+// The stream of the next direct-path plain decode.  The extra streams are made
+// on first use (a loader that never decodes in place -- copy path, tile16,
+// colour kernel -- keeps its single stream).  The decode table was uploaded
+// with blocking copies long before, and whatever else the loader stream holds
+// at that moment is waited for once, so every stream sees complete tables.
+hipStream_t StreamLoader::next_decode_stream() {
+  if (decode_streams_.empty()) {
+    decode_streams_.push_back(stream_);
+    if (cfg_.decode_streams > 1) check(hipStreamSynchronize(stream_), "hipStreamSynchronize(loader stream)");
+    for (int k = 1; k < cfg_.decode_streams; ++k) {
+      hipStream_t s;
+      check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate(decode)");
+      decode_streams_.push_back(s);
+    }
+  }
+  return decode_streams_[decode_rr_++ % decode_streams_.size()];
+}
+
 // Launch coalescing: a direct-path batch launches at once while fewer than
 // kMaxInflight launches are queued on the loader stream; otherwise it waits,
 // and when a launch retires every waiting batch goes out in ONE kernel
-// (per-image source/destination pointers).  When the GPU side is the
+// (per-image source/destination pointers); "queued" counts the launches in
+// flight over all decode streams.  When the GPU side is the
 // bottleneck the launches therefore grow -- fewer ramp-up/tail phases per
 // image -- and when the producers are, every batch still launches at once.
 void StreamLoader::flush_pending(bool force) {
@@ -1031,9 +1059,15 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   const double t_issue = now_ms();
   const bool direct = group.front().direct;
   int total = 0;
+  // a plain decode of host-resident frames (one kernel, or one per source
+  // layout) takes the next decode stream in turn; all the launch's stream-side
+  // work below -- post-event waits, timing and completion events, kernels --
+  // goes to that one stream.  Everything else stays on the loader stream
+  const bool plain = direct && !cfg_.color_matrix && !group.front().tiled;
+  const hipStream_t st = plain ? next_decode_stream() : stream_;
   for (auto& b : group) {
     if (cfg_.host_sync) host_wait(b.ready);   // the consumer is done with the buffer
-    else check(hipStreamWaitEvent(stream_, b.ready, 0), "hipStreamWaitEvent(post)");
+    else check(hipStreamWaitEvent(st, b.ready, 0), "hipStreamWaitEvent(post)");
     (void)hipEventDestroy(b.ready);
     total += int(b.items.size());
   }
@@ -1056,7 +1090,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   const int64_t launch_no = ++launch_no_;
   // skip the cold first launches (allocation, code-object load, page faults)
   if (launch_no > kTimedSkip && launch_no % kTimedEvery == 0 && hipEventCreate(&t0) == hipSuccess) {
-    if (hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, stream_) != hipSuccess) {
+    if (hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, st) != hipSuccess) {
       (void)hipEventDestroy(t0);
       if (t1) (void)hipEventDestroy(t1);
       t0 = t1 = nullptr;
@@ -1220,7 +1254,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
           }
         sp.B = sp.nsrcs = sp.ndsts = n;
         sp.Cin = pl == 1 ? 3 : C_;
-        e = decode(sp, stream_);
+        e = decode(sp, st);
       }
       // (stats_.launches counts launch groups: this one stays one coalesced
       // launch for the batches in it, run as two kernels)
@@ -1237,11 +1271,11 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       }
       e = decode_tiles(dp, tp, stream_);
     } else {
-      e = decode(dp, stream_);
+      e = decode(dp, st);
     }
   }
   check(e, "decode kernel launch");
-  if (direct) add_event(stream_);
+  if (direct) add_event(st);
   if (!direct && !passthrough && !copy_streams_.empty()) {
     if (stage_free_.size() < staging_.size()) stage_free_.resize(staging_.size(), nullptr);
     if (!stage_free_[stage_idx])
@@ -1253,7 +1287,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     (void)hipEventDestroy(t1);
     t0 = t1 = nullptr;
   }
-  if (t0) check(hipEventRecord(t1, stream_), "hipEventRecord(t1)");
+  if (t0) check(hipEventRecord(t1, st), "hipEventRecord(t1)");
   Inflight fl;
   fl.launch_no = launch_no;
   fl.t0 = t0, fl.t1 = t1, fl.images = total;
@@ -1277,16 +1311,20 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     }
     if (host_passthrough) {
       rb.pending = copied;        // the DMA is all the batch's device work
+    } else if (direct && cfg_.host_sync) {
+      // every batch of the group completes where the group's `copied` event
+      // sits (right behind the kernel): one marker per launch, owned jointly
+      rb.pending = copied;
     } else if (cfg_.host_sync) {
       auto fin = std::make_shared<EventSet>();
       hipEvent_t ev;
       check(hipEventCreateWithFlags(&ev, completion_event_flags()), "hipEventCreate(done)");
-      check(hipEventRecord(ev, stream_), "hipEventRecord(done)");
+      check(hipEventRecord(ev, st), "hipEventRecord(done)");
       fin->ev.push_back(ev);
       rb.pending = fin;
     } else {
       check(hipEventCreateWithFlags(&rb.done, hipEventDisableTiming), "hipEventCreate(done)");
-      check(hipEventRecord(rb.done, stream_), "hipEventRecord(done)");
+      check(hipEventRecord(rb.done, st), "hipEventRecord(done)");
     }
     rb.recv_ms = t_issue - b.t0;
     done.push_back(std::move(rb));

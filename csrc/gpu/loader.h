@@ -21,7 +21,8 @@
 //     -> the kernel (flip/gamma/unpack/normalize/CHW|NHWC) writes the
 //        consumer's tensor on a private non-blocking HIP stream; an event
 //        after the last host read lets the worker hand slots back (no host
-//        callback in the stream); a per-batch event marks it ready
+//        callback in the stream); the same event (direct path, host-ordered)
+//        or a per-batch event marks the batch ready
 //     -> consumer (Python) takes batch j; its torch stream waits on the event.
 //
 // Backpressure is preserved end to end: when the consumer stops posting
@@ -115,6 +116,18 @@ struct LoaderConfig {
   // Direct-path launches queued on the loader stream before new batches wait
   // and coalesce into one launch (0: always hold until 64 images or stream end).
   int launch_depth = 2;
+  // Direct-path plain-decode launch groups rotate over this many non-blocking
+  // HIP streams (1..4; 1: everything on the loader stream).  With 2, launch
+  // N+1 sits on another hardware queue than launch N and no completion marker
+  // of N stands in front of its kernel.  Back-to-back decodes without
+  // producers gain 3-6 % that way, but in the streaming pipeline the two
+  // launches that `launch_depth` = 2 allows then run side by side, share the
+  // link, end together and leave it idle until the host has queued the next
+  // pair: 8 % slower than one stream (profiles/r8/decode_overlap.md), hence
+  // the default.  `launch_depth` counts the launches in flight over all
+  // streams.  Copy-path, pass-through, tile16 and colour-kernel launches
+  // always use the loader stream.
+  int decode_streams = 1;
   // Order the loader's work against the consumer on the HOST: a posted
   // buffer is written only once the host has seen its post event complete,
   // and a batch is handed out only once the host has seen all its device
@@ -285,6 +298,7 @@ class StreamLoader {
   void launch();
   void flush_pending(bool force);
   void launch_group(std::vector<Pending>& group);
+  hipStream_t next_decode_stream();
   void reap(bool wait_all = false);   // release pinned slots of completed H2D copies
   void evict_keys();
   void drain_sockets();               // stop(): hand back ring slots of still-queued descriptors
@@ -320,6 +334,7 @@ class StreamLoader {
   std::vector<Item> cur_;
   std::deque<Pending> pending_;
   int pending_images_ = 0;
+  static constexpr int kMaxDecodeStreams = 4;
   static constexpr int kTimedEvery = 4;
   static constexpr int kTimedSkip = 8;         // cold launches never sampled
   static constexpr int64_t kKeyIdleLaunches = 64;
@@ -327,6 +342,11 @@ class StreamLoader {
   double last_reap_ms_ = 0;
   std::vector<hipStream_t> copy_streams_;      // copy path fan-out (cfg_.copy_streams > 1)
   std::vector<hipEvent_t> copy_done_;          // one per copy stream, reused
+  // direct-path plain decodes rotate over these (cfg_.decode_streams); [0] is
+  // stream_, the others are owned here and made on first use.  Each launch keeps all its stream-side
+  // work (post-event waits, timing and completion events, kernels) on one of them
+  std::vector<hipStream_t> decode_streams_;
+  size_t decode_rr_ = 0;
   std::vector<hipEvent_t> stage_free_;         // per staging buffer: last kernel reading it
   std::vector<shm::Segment*> seg_list_;        // mapped rings, for stats() (guarded by mu_)
   // the configured decode is the identity on the frame bytes (u8, NHWC, all

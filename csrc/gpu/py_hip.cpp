@@ -1009,6 +1009,81 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("mode"), py::arg("kind"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("iters"),
         py::arg("max_grid") = 0, py::arg("copy_streams") = 1, py::arg("pipelined") = false);
 
+  // What overlapping consecutive direct decodes is worth without producers:
+  // `iters` decodes of B host-resident frames (mmap + hipHostRegister, like
+  // the producers' rings) are queued with no host synchronisation in between,
+  // launch i on stream i % streams, each stream writing an output of its own.
+  // Every launch leaves one completion event behind its kernel, as the
+  // loader's launches do.  Returns (us per launch, GB/s of frame bytes, bad):
+  // `bad` counts images of either output whose first and last pixel do not
+  // hold the frame's bytes.
+  m.def("bench_decode_overlap",
+        [](int B, int H, int W, int Cin, int iters, int streams) {
+          py::gil_scoped_release nogil;
+          if (B < 1 || B > kMaxSrcs || (Cin != 3 && Cin != 4) || iters < 1 || streams < 1 || streams > 4)
+            throw std::invalid_argument("bench_decode_overlap: B 1..64, Cin 3 or 4, streams 1..4");
+          const size_t npix = size_t(H) * W;
+          const size_t img = npix * size_t(Cin);
+          const size_t slot = (img + 4095) & ~size_t(4095);
+          uint8_t* host = static_cast<uint8_t*>(
+              mmap(nullptr, slot * B, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0));
+          if (host == MAP_FAILED) throw std::runtime_error("bench_decode_overlap: mmap failed");
+          for (size_t i = 0; i < slot * size_t(B); ++i) host[i] = uint8_t(i * 7);
+          check(hipHostRegister(host, slot * B, hipHostRegisterMapped), "hipHostRegister");
+          uint8_t* dev_host = nullptr;
+          check(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev_host), host, 0), "hipHostGetDevicePointer");
+          const size_t out_floats = size_t(B) * 3 * npix;
+          float *dst = nullptr, *lut = nullptr;
+          check(hipMalloc(reinterpret_cast<void**>(&dst), out_floats * sizeof(float) * size_t(streams)), "hipMalloc");
+          std::vector<float> hl(kTableFloats, 0.f);   // identity table, mode 0 header
+          for (int i = 0; i < 4 * 256; ++i) hl[size_t(i)] = float(i & 255);
+          check(hipMalloc(reinterpret_cast<void**>(&lut), hl.size() * sizeof(float)), "hipMalloc");
+          check(hipMemcpy(lut, hl.data(), hl.size() * sizeof(float), hipMemcpyHostToDevice), "lut");
+          std::vector<hipStream_t> ss(size_t(streams), nullptr);
+          for (auto& s : ss) check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "stream");
+          DecodeParams p;
+          p.lut = lut;
+          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = 3;
+          p.nsrcs = B;
+          for (int b = 0; b < B; ++b) p.srcs[b] = dev_host + size_t(b) * slot;
+          std::vector<hipEvent_t> evs;
+          evs.reserve(size_t(iters));
+          auto run = [&](int i, bool mark) {
+            const size_t k = size_t(i) % size_t(streams);
+            p.dst = dst + k * out_floats;
+            check(decode(p, ss[k]), "decode");
+            if (!mark) return;
+            hipEvent_t ev;
+            check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "event");
+            check(hipEventRecord(ev, ss[k]), "record");
+            evs.push_back(ev);
+          };
+          for (int i = 0; i < 2 * streams; ++i) run(i, false);
+          for (auto s : ss) check(hipStreamSynchronize(s), "sync");
+          auto t0 = std::chrono::steady_clock::now();
+          for (int i = 0; i < iters; ++i) run(i, true);
+          for (auto s : ss) check(hipStreamSynchronize(s), "sync");
+          double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / iters;
+          for (auto ev : evs) (void)hipEventDestroy(ev);
+          int bad = 0;
+          for (int k = 0; k < streams; ++k)
+            for (int b = 0; b < B; ++b) {
+              float v[2] = {0.f, 0.f};
+              const float* o = dst + size_t(k) * out_floats + size_t(b) * 3 * npix;
+              check(hipMemcpy(&v[0], o, sizeof(float), hipMemcpyDeviceToHost), "d2h");
+              check(hipMemcpy(&v[1], o + npix - 1, sizeof(float), hipMemcpyDeviceToHost), "d2h");
+              const uint8_t* f = host + size_t(b) * slot;
+              if (v[0] != float(f[0]) || v[1] != float(f[(npix - 1) * size_t(Cin)])) ++bad;
+            }
+          for (auto s : ss) (void)hipStreamDestroy(s);
+          (void)hipFree(dst);
+          (void)hipFree(lut);
+          (void)hipHostUnregister(host);
+          munmap(host, slot * B);
+          return std::make_tuple(us, double(img) * B / us / 1e3, bad);
+        },
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("iters"), py::arg("streams") = 1);
+
   // Kernel-only timing (no Python launch overhead): `iters` back-to-back
   // decode launches between two HIP events; returns microseconds per launch.
   m.def("bench_decode",
@@ -1078,9 +1153,10 @@ PYBIND11_MODULE(_hip, m) {
                        int out_dtype, int layout, std::vector<float> lut, std::vector<float> matrix,
                        std::vector<float> bias, bool direct, int launch_depth, int copy_streams, bool host_sync,
                        std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed,
-                       bool planar_alpha) {
+                       bool planar_alpha, int decode_streams) {
              LoaderConfig c;
              c.direct = direct;
+             c.decode_streams = decode_streams;
              c.planar_alpha = planar_alpha;
              c.host_sync = host_sync;
              c.copy_streams = copy_streams;
@@ -1124,7 +1200,8 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"), py::arg("lut"), py::arg("matrix"),
            py::arg("bias"), py::arg("direct") = true, py::arg("launch_depth") = 2,
            py::arg("copy_streams") = 2, py::arg("host_sync") = true, py::arg("matrices") = std::vector<float>(),
-           py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0, py::arg("planar_alpha") = true)
+           py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0, py::arg("planar_alpha") = true,
+           py::arg("decode_streams") = 1)
       .def("start", &StreamLoader::start)
       .def("wait_shape",
            [](StreamLoader& l, long timeout_ms) -> py::object {

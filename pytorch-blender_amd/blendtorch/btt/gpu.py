@@ -40,6 +40,8 @@ logger = logging.getLogger('blendtorch')
 
 __all__ = ['DeviceLoader', 'DecodeConfig']
 
+DEFAULT_DECODE_STREAMS = 1   # csrc/gpu/loader.h LoaderConfig::decode_streams
+
 
 def _default_io_threads(addresses) -> int:
     n = len(addresses)
@@ -103,6 +105,14 @@ class DeviceLoader:
         together in one launch (fewer kernel ramp-up/tail phases when the GPU
         side is the bottleneck).  0: hold batches until 64 images are pending
         or the stream ends (tests / maximal coalescing).
+    decode_streams: int, optional
+        (default: 1, or ``BT_LOADER_DECODE_STREAMS``.)  Direct-path decode
+        launches rotate over this many HIP streams (1..4), so consecutive
+        launches sit on different hardware queues and may run side by side.
+        ``launch_depth`` counts launches over all of them, and batches are
+        still delivered in launch order.  Measured slower than one stream in
+        the streaming pipeline (profiles/r8/decode_overlap.md): with
+        ``launch_depth`` 2 both launches share the link and end together.
     copy_streams: int
         Copy path (``h2d='copy'`` or frames that are not device-visible): the
         frames of a batch are spread over this many HIP streams so several
@@ -137,9 +147,16 @@ class DeviceLoader:
                  skip_bad: bool = False, meta_to_device: bool = False, staging_depth: int = 3, h2d: str = 'auto',
                  launch_depth: int = 2, log_every: Optional[float] = None, copy_streams: int = 2,
                  defer_post: bool = False, host_sync: Optional[bool] = None, reuse_buffers: bool = False,
-                 shm_alpha: str = 'auto'):
+                 shm_alpha: str = 'auto', decode_streams: Optional[int] = None):
         if h2d not in ('auto', 'copy'):
             raise ValueError("h2d must be 'auto' or 'copy'")
+        # None: the native default (1), or the BT_LOADER_DECODE_STREAMS diagnostic
+        # (the same build run both ways); an explicit argument always wins
+        if decode_streams is None:
+            decode_streams = int(os.environ.get('BT_LOADER_DECODE_STREAMS') or DEFAULT_DECODE_STREAMS)
+        if not 1 <= int(decode_streams) <= 4:
+            raise ValueError('decode_streams must be 1..4')
+        self.decode_streams = int(decode_streams)
         if shm_alpha not in ('auto', 'interleaved'):
             raise ValueError("shm_alpha must be 'auto' or 'interleaved'")
         self.h2d = h2d
@@ -240,7 +257,7 @@ class DeviceLoader:
             max_batches, 0, 0, self.staging_depth, self.skip_bad, cfg.cout, list(cfg.cmap) + [0] * (4 - len(cfg.cmap)),
             int(cfg.flip), ops.OUT_DTYPES[cfg.dtype], ops.LAYOUTS[cfg.layout], lut, matrix, bias,
             self.h2d == 'auto', self.launch_depth, self.copy_streams, self.host_sync, matrices, jitter, seed,
-            self.shm_alpha == 'auto')
+            self.shm_alpha == 'auto', self.decode_streams)
 
     def _post(self, loader, stream):
         shape = self.decode.out_shape(self.batch_size, *self.shape[:2])
