@@ -10,11 +10,13 @@
 
 #include <chrono>
 #include <tuple>
+#include <type_traits>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <sys/mman.h>
 
+#include "../codec/tiledelta.h"
 #include "../python/pyvalue.h"
 #include "comm.h"
 #include "kernels.h"
@@ -141,6 +143,23 @@ void fill_cmap(int* dst, const std::vector<int>& cmap) {
   for (size_t i = 0; i < 4; ++i) dst[i] = i < cmap.size() ? cmap[i] : int(i);
 }
 
+// Per-image launch parameters of DecodeParams / Color4x4Params from Python lists
+// (device pointers as integers): srcs / dsts of up to kMaxSrcs entries, up to 4
+// flip_bits words.  Empty lists leave the dense src / dst form.
+template <typename P>
+void fill_image_lists(P& p, const std::vector<uintptr_t>& srcs, const std::vector<uintptr_t>& dsts,
+                      const std::vector<uint64_t>& flip_bits, const char* what) {
+  if (srcs.size() > size_t(kMaxSrcs) || dsts.size() > size_t(kMaxSrcs))
+    throw std::invalid_argument(std::string(what) + ": srcs / dsts hold at most kMaxSrcs (64) pointers");
+  if (flip_bits.size() > 4) throw std::invalid_argument(std::string(what) + ": flip_bits holds at most 4 words");
+  using D = typename std::remove_pointer<typename std::remove_reference<decltype(p.dsts[0])>::type>::type;
+  p.nsrcs = int(srcs.size());
+  for (size_t i = 0; i < srcs.size(); ++i) p.srcs[i] = ptr<const uint8_t>(srcs[i]);
+  p.ndsts = int(dsts.size());
+  for (size_t i = 0; i < dsts.size(); ++i) p.dsts[i] = ptr<D>(dsts[i]);
+  for (size_t i = 0; i < flip_bits.size(); ++i) p.flip_bits[i] = flip_bits[i];
+}
+
 }  // namespace
 
 // a deferred weight-gradient slice reduce (ConvWgradParams::Reduce) as a
@@ -223,8 +242,12 @@ PYBIND11_MODULE(_hip, m) {
   m.def("decode",
         [](uintptr_t src, uintptr_t src_offsets, uintptr_t dst, uintptr_t lut, uintptr_t flip, int B, int H, int W,
            int Cin, int Cout, std::vector<int> cmap, int flip_all, int out_dtype, int layout, uintptr_t stream,
-           bool src_offsets_aligned) {
+           bool src_offsets_aligned, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts,
+           std::vector<uint64_t> flip_bits, int max_grid, int unroll) {
           DecodeParams p;
+          fill_image_lists(p, srcs, dsts, flip_bits, "decode");
+          p.max_grid = max_grid;
+          p.unroll = unroll;
           p.src = ptr<const uint8_t>(src);
           p.src_offsets = ptr<const int64_t>(src_offsets);
           p.src_offsets_aligned = src_offsets_aligned;
@@ -240,15 +263,53 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("src"), py::arg("src_offsets"), py::arg("dst"), py::arg("lut"), py::arg("flip"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"),
-        py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("src_offsets_aligned") = false);
+        py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("src_offsets_aligned") = false,
+        py::arg("srcs") = std::vector<uintptr_t>(), py::arg("dsts") = std::vector<uintptr_t>(),
+        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0, py::arg("unroll") = 0);
+
+  // Key-frame delta decode (kernels.h: decode_tiles) at the pointer level: srcs[b] the encoded frame,
+  // fills[b] image b's decoded key frame, tile_start the prefix sums of the payload tile counts.
+  m.def("decode_tiles",
+        [](std::vector<uintptr_t> srcs, std::vector<uintptr_t> fills, std::vector<int> tile_start, uintptr_t dst,
+           uintptr_t lut, uintptr_t flip, int B, int H, int W, int Cin, int Cout, std::vector<int> cmap, int flip_all,
+           int out_dtype, int layout, uintptr_t stream, std::vector<uintptr_t> dsts, std::vector<uint64_t> flip_bits,
+           int max_grid) {
+          DecodeParams p;
+          fill_image_lists(p, srcs, dsts, flip_bits, "decode_tiles");
+          if (fills.size() > size_t(kMaxSrcs) || tile_start.size() > size_t(kMaxSrcs) + 1)
+            throw std::invalid_argument("decode_tiles: fills / tile_start hold at most kMaxSrcs (64) images");
+          if (H <= 0 || W <= 0) throw std::invalid_argument("decode_tiles: H and W must be positive");
+          TileParams t;
+          for (size_t i = 0; i < fills.size(); ++i) t.fills[i] = ptr<const void>(fills[i]);
+          for (size_t i = 0; i < tile_start.size(); ++i) t.tile_start[i] = tile_start[i];
+          const size_t elem = out_dtype == OUT_F32 ? 4 : (out_dtype == OUT_U8 ? 1 : 2);
+          t.out_img_bytes = int64_t(size_t(H) * size_t(W) * size_t(Cout) * elem);
+          t.payload_off = int64_t(tiledelta::payload_offset(H, W));
+          p.max_grid = max_grid;
+          p.dst = ptr<void>(dst);
+          p.lut = ptr<const float>(lut);
+          p.flip = ptr<const uint8_t>(flip);
+          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+          fill_cmap(p.cmap, cmap);
+          p.flip_all = flip_all;
+          p.out_dtype = out_dtype;
+          p.layout = layout;
+          check(decode_tiles(p, t, stream_of(stream)), "decode_tiles");
+        },
+        py::arg("srcs"), py::arg("fills"), py::arg("tile_start"), py::arg("dst"), py::arg("lut"), py::arg("flip"),
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("cmap"),
+        py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"), py::arg("stream"),
+        py::arg("dsts") = std::vector<uintptr_t>(), py::arg("flip_bits") = std::vector<uint64_t>(),
+        py::arg("max_grid") = 0);
 
   m.def("replay_sample",
         [](uintptr_t store, int64_t count, uintptr_t dst, uintptr_t lut, int B, int H, int W, int Cin, int Cout,
            std::vector<int> cmap, int flip_all, int out_dtype, int layout, uint64_t seed, uintptr_t counter,
            uint64_t ctr_value, uintptr_t index_in, uintptr_t index_out, std::vector<uintptr_t> meta_src, std::vector<uintptr_t> meta_dst,
-           std::vector<int> meta_bytes, uintptr_t stream, int xf_table_only) {
+           std::vector<int> meta_bytes, uintptr_t stream, int xf_table_only, int max_grid) {
           DecodeParams p;
           p.xf_table_only = xf_table_only;
+          p.max_grid = max_grid;
           p.src = ptr<const uint8_t>(store);
           p.dst = ptr<void>(dst);
           p.lut = ptr<const float>(lut);
@@ -279,7 +340,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("store"), py::arg("count"), py::arg("dst"), py::arg("lut"), py::arg("B"), py::arg("H"), py::arg("W"),
         py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"),
         py::arg("seed"), py::arg("counter"), py::arg("ctr_value"), py::arg("index_in"), py::arg("index_out"), py::arg("meta_src"),
-        py::arg("meta_dst"), py::arg("meta_bytes"), py::arg("stream"), py::arg("xf_table_only") = 0);
+        py::arg("meta_dst"), py::arg("meta_bytes"), py::arg("stream"), py::arg("xf_table_only") = 0,
+        py::arg("max_grid") = 0);
 
   m.def("multi_cast",
         [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst, std::vector<int64_t> numel, int mode,
@@ -699,8 +761,21 @@ PYBIND11_MODULE(_hip, m) {
   m.def("color4x4",
         [](uintptr_t src, uintptr_t dst, uintptr_t lut, uintptr_t M, uintptr_t bias, uintptr_t flip, int B, int H,
            int W, int Cout, int flip_all, uintptr_t stream, int mat_mode, uintptr_t Ms, std::vector<float> jitter,
-           float pivot) {
+           float pivot, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts, std::vector<uint64_t> flip_bits,
+           std::vector<int> mat_pos) {
           Color4x4Params p;
+          fill_image_lists(p, srcs, dsts, flip_bits, "color4x4");
+          if (mat_mode == kColorPos) {
+            if (B > kMaxSrcs || mat_pos.size() != size_t(B))
+              throw std::invalid_argument("color4x4: mat_pos needs one matrix index per image, B <= 64");
+            for (int b = 0; b < B; ++b) {
+              if (mat_pos[size_t(b)] < 0 || mat_pos[size_t(b)] > 255)
+                throw std::invalid_argument("color4x4: a mat_pos index is a u8");
+              p.mat_pos[b] = uint8_t(mat_pos[size_t(b)]);
+            }
+          } else if (!mat_pos.empty()) {
+            throw std::invalid_argument("color4x4: mat_pos goes with mat_mode 1 (kColorPos)");
+          }
           p.src = ptr<const uint8_t>(src);
           p.dst = ptr<float>(dst);
           p.lut = ptr<const float>(lut);
@@ -722,7 +797,9 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("src"), py::arg("dst"), py::arg("lut"), py::arg("M"), py::arg("bias"), py::arg("flip"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("Cout"), py::arg("flip_all"), py::arg("stream"), py::arg("mat_mode") = 0,
-        py::arg("Ms") = 0, py::arg("jitter") = std::vector<float>(), py::arg("pivot") = 0.5f);
+        py::arg("Ms") = 0, py::arg("jitter") = std::vector<float>(), py::arg("pivot") = 0.5f,
+        py::arg("srcs") = std::vector<uintptr_t>(), py::arg("dsts") = std::vector<uintptr_t>(),
+        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("mat_pos") = std::vector<int>());
 
   m.def("project",
         [](uintptr_t pts, int64_t N, uintptr_t PV, uintptr_t V, int W, int H, int upper_left, uintptr_t out_px,

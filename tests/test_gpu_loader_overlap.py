@@ -84,7 +84,9 @@ def _fixed_pose_run(dev, port, cfg, producers, nbatch, **kw):
 
 def _one_stream_image(dev, port, name):
     if name not in _first:
-        imgs, st = _fixed_pose_run(dev, port, _CFGS[name](), [RES + POSE + ['--shm', '8']] * 2, 4, decode_streams=1)
+        # 32 frames over 2 x 8 ring slots: a producer can fill its ring before the loader maps it and leaves
+        # its hint, so only frames past the rings' capacity are sure to be planar (16 frames gave none, once)
+        imgs, st = _fixed_pose_run(dev, port, _CFGS[name](), [RES + POSE + ['--shm', '8']] * 2, 8, decode_streams=1)
         assert st['planar_frames'] > 0, st
         assert all(torch.equal(i, imgs[0][0]) for b in imgs for i in b)   # one pose: one image
         _first[name] = imgs[0][0]
