@@ -89,6 +89,23 @@ struct DecodeParams {
 };
 hipError_t decode(const DecodeParams& p, hipStream_t stream);
 
+// decode() of a window of every image, optionally mirrored left-right.  With
+// full[b] what decode() delivers for image b (upright after its flip):
+//   out[b, c, i, j] = full[b, c, y0[b] + i, x0[b] + (m_b ? w - 1 - j : j)]   0 <= i < h, 0 <= j < w
+// (y0, x0: upper-left corner in the upright image; m_b: bit b of mirror_bits;
+// a flipped source is read at row H - 1 - (y0 + i)).  p.H, p.W stay the SOURCE
+// frame size; the output image is Cout * h * w elements, dense or dsts[b].
+// Only the window's bytes are read -- in place, also from host memory.
+// Values are bit-identical to decode()'s.  p.B <= kMaxSrcs; a window that
+// leaves the frame, or a bad channel map, is hipErrorInvalidValue (checked on
+// the host: nothing is launched).  p.unroll is ignored.
+struct CropParams {
+  int h = 0, w = 0;
+  int16_t y0[kMaxSrcs] = {}, x0[kMaxSrcs] = {};
+  uint64_t mirror_bits = 0;
+};
+hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t stream);
+
 // Key-frame delta frames (csrc/codec/tiledelta.h), decoded in two launches
 // on `stream` with the same table, channel map, dtype and layout as decode():
 //   1. output image b <- fills[b]: its producer's key frame, already decoded

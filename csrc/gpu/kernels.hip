@@ -481,6 +481,171 @@ __global__ __launch_bounds__(kBlock) void decode_scalar_kernel(DecodeParams p) {
   }
 }
 
+// ---- crop + mirror (kernels.h: decode_crop) --------------------------------
+// The same value path as decode(); only the addressing differs: a lane owns
+// PPT consecutive pixels of one WINDOW row, read in place from the source
+// frame at window row i -> frame row y0 + i (then the flip), window column j
+// -> frame column x0 + j, or x0 + w - 1 - j when the image is mirrored.
+
+// NW dwords from a dword-aligned address, widest loads first
+template <int NW>
+__device__ __forceinline__ void load_words(const uint8_t* a0, uint32_t (&t)[NW + 1]) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  const uint32_t* s = static_cast<const uint32_t*>(__builtin_assume_aligned(a0, 4));
+#pragma unroll
+  for (int i = 0; i + 4 <= NW; i += 4) {
+    u32x4 q;
+    __builtin_memcpy(&q, s + i, 16);
+    t[i] = q.x, t[i + 1] = q.y, t[i + 2] = q.z, t[i + 3] = q.w;
+  }
+  constexpr int R = NW % 4, O = NW - R;
+  if constexpr (R >= 2) {
+    u32x2 q;
+    __builtin_memcpy(&q, s + O, 8);
+    t[O] = q.x, t[O + 1] = q.y;
+  }
+  if constexpr (R == 1 || R == 3) t[NW - 1] = s[NW - 1];
+}
+
+// The lane's PPT * CIN bytes from `a`.  CIN == 4: `a` is dword aligned.
+// CIN == 3: `a` is only byte aligned (a window may start at any column), so
+// the lane reads the dwords its bytes lie in and shifts them into place with
+// a byte funnel shift.  Those are the dwords [a0, a0 + 4 NW) with a0 = a & ~3,
+// and, when a != a0, the one behind them: a0 holds the lane's first byte, and
+// with a != a0 its last byte a + 4 NW - 1 lies in [a0 + 4 NW, a0 + 4 NW + 4).
+// So no lane reads a dword without a byte of its own pixels, and as the
+// frame's H * W * 3 bytes (W % 4 == 0) end on a dword boundary of its
+// 16-byte aligned base, the last window row of the last frame row never
+// reads past H * W * CIN.
+template <int PPT, int CIN>
+__device__ __forceinline__ void load_window_pixels(const uint8_t* a, Pixels<PPT, CIN>& px) {
+  constexpr int NW = Pixels<PPT, CIN>::NW;
+  uint32_t t[NW + 1];
+  if constexpr (CIN == 4) {
+    load_words<NW>(a, t);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) px.w[k] = t[k];
+  } else {
+    const uint32_t s = uint32_t(reinterpret_cast<uintptr_t>(a)) & 3u;
+    const uint8_t* a0 = a - s;
+    load_words<NW>(a0, t);
+    t[NW] = 0;
+    if (s) t[NW] = *reinterpret_cast<const uint32_t*>(a0 + 4 * NW);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) px.w[k] = __builtin_amdgcn_alignbyte(t[k + 1], t[k], s);
+  }
+}
+
+// Reverse the order of the lane's PPT pixels (every index a compile-time
+// constant once unrolled: shifts and ors on registers, no scratch).
+template <int PPT, int CIN>
+__device__ __forceinline__ void reverse_pixels(Pixels<PPT, CIN>& px) {
+  constexpr int NW = Pixels<PPT, CIN>::NW;
+  if constexpr (CIN == 4) {
+#pragma unroll
+    for (int k = 0; k < NW / 2; ++k) {
+      const uint32_t u = px.w[k];
+      px.w[k] = px.w[NW - 1 - k];
+      px.w[NW - 1 - k] = u;
+    }
+  } else {
+    static_assert(CIN == 3, "packed RGB");
+    uint32_t pix[PPT];
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+      const int k = (3 * i) >> 2, sh = (3 * i) & 3;
+      const int k1 = k + 1 < NW ? k + 1 : k;
+      const uint32_t lo = px.w[k] >> (8 * sh);
+      pix[i] = (sh >= 2 ? lo | (px.w[k1] << (8 * (4 - sh))) : lo) & 0xFFFFFFu;
+    }
+    uint32_t o[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) o[k] = 0;
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+      const int k = (3 * i) >> 2, sh = (3 * i) & 3;
+      const uint32_t r = pix[PPT - 1 - i];
+      o[k] |= r << (8 * sh);
+      if (sh >= 2) o[k + 1 < NW ? k + 1 : k] |= r >> (8 * (4 - sh));
+    }
+#pragma unroll
+    for (int k = 0; k < NW; ++k) px.w[k] = o[k];
+  }
+}
+
+__device__ __forceinline__ bool image_flipped(const DecodeParams& p, int b) {
+  return p.flip_all || (p.flip && p.flip[b]) || (b < 256 && ((p.flip_bits[b >> 6] >> (b & 63)) & 1));
+}
+
+template <int PPT, int CIN, int OUTT, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void decode_crop_kernel(DecodeParams p, CropParams c) {
+  __shared__ uint32_t tab[kTabWords];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  __syncthreads();
+
+  const int64_t HW = int64_t(p.H) * p.W;       // source frame
+  const int64_t hw = int64_t(c.h) * c.w;       // window = output image
+  const int64_t groups_per_img = hw / PPT;
+  const int64_t total = groups_per_img * p.B;
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cm[k] = p.cmap[k];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  const bool small = total + stride < (int64_t(1) << 31);
+
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += stride) {
+    Group gr;
+    int i, j;   // window row, first window column
+    split_group<PPT>(g, groups_per_img, c.w, small, gr.b, gr.q, i, j);
+    const int b = gr.b;
+    const int y = int(c.y0[b]) + i;
+    const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
+    // the mirror bit is per image and a wave may straddle two images: the
+    // mirrored lanes read the PPT source pixels that end the row's mirror
+    // image of their group and reverse them (a branch into a static body)
+    const bool mirror = (c.mirror_bits >> b) & 1;
+    const int xs = int(c.x0[b]) + (mirror ? c.w - PPT - j : j);
+    const uint8_t* img = p.nsrcs ? p.srcs[b] : p.src + (p.src_offsets ? p.src_offsets[b] : int64_t(b) * HW * CIN);
+    gr.src = img + (int64_t(sy) * p.W + xs) * CIN;
+    Pixels<PPT, CIN> px;
+    load_window_pixels<PPT, CIN>(gr.src, px);
+    if (mirror) reverse_pixels<PPT, CIN>(px);
+    emit<PPT, CIN, OUTT, LAYOUT>(p, xf, cm, cout, hw, gr, px);
+  }
+}
+
+// Crop-aware fallback: one window pixel per thread (any size, any alignment).
+template <int OUTT>
+__global__ __launch_bounds__(kBlock) void decode_crop_scalar_kernel(DecodeParams p, CropParams c) {
+  __shared__ uint32_t tab[kTabWords];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  __syncthreads();
+  const int64_t HW = int64_t(p.H) * p.W;
+  const int64_t hw = int64_t(c.h) * c.w;
+  const int64_t total = hw * p.B;
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += int64_t(gridDim.x) * kBlock) {
+    const int b = int(g / hw);
+    const int64_t q = g - int64_t(b) * hw;
+    const int i = int(q / c.w), j = int(q - int64_t(i) * c.w);
+    const int y = int(c.y0[b]) + i;
+    const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
+    const int x = int(c.x0[b]) + (((c.mirror_bits >> b) & 1) ? c.w - 1 - j : j);
+    const uint8_t* img = p.nsrcs ? p.srcs[b] : p.src + (p.src_offsets ? p.src_offsets[b] : int64_t(b) * HW * p.Cin);
+    const uint8_t* s = img + (int64_t(sy) * p.W + x) * p.Cin;
+    for (int k = 0; k < p.Cout; ++k) {
+      const float v = xf_value(xf, k, s[p.cmap[k]]);
+      const int64_t off = p.layout == NCHW ? int64_t(k) * hw + q : q * p.Cout + k;   // within image b
+      const int64_t ie = hw * p.Cout;
+      if constexpr (OUTT == OUT_F32) image_out<float>(p, b, ie)[off] = v;
+      else if constexpr (OUTT == OUT_BF16) image_out<uint16_t>(p, b, ie)[off] = f2bf(v);
+      else if constexpr (OUTT == OUT_F16) image_out<uint16_t>(p, b, ie)[off] = f2h(v);
+      else image_out<uint8_t>(p, b, ie)[off] = uint8_t(v);
+    }
+  }
+}
+
 int grid_for(int64_t work, int cap = 0) {
   // Measured on MI355X (profiles/decode_unroll_sweep.txt): up to ~4k blocks
   // of work, one resident wave of 2048 blocks (256 CUs x 8) is best; for
@@ -589,6 +754,66 @@ hipError_t decode(const DecodeParams& p, hipStream_t stream) {
     case OUT_BF16: return launch_out<OUT_BF16>(p, stream);
     case OUT_F16: return launch_out<OUT_F16>(p, stream);
     case OUT_U8: return launch_out<OUT_U8>(p, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+namespace {
+
+template <int PPT, int CIN, int OUTT>
+void launch_crop_vec(const DecodeParams& p, const CropParams& c, hipStream_t s) {
+  const int grid = grid_for(int64_t(p.B) * c.h * c.w / PPT, p.max_grid);
+  if (p.layout == NCHW)
+    decode_crop_kernel<PPT, CIN, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, c);
+  else
+    decode_crop_kernel<PPT, CIN, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, c);
+}
+
+template <int OUTT>
+hipError_t launch_crop_out(const DecodeParams& p, const CropParams& c, hipStream_t s) {
+  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  // vector path: a lane's PPT pixels sit in one window row, every image's
+  // source misalignment is a whole number of bytes below a dword of a
+  // 16-byte aligned frame whose rows are dword multiples, and the 16-byte
+  // plane / pixel-run stores are aligned
+  const bool src_aligned = p.nsrcs ? srcs_ok(p.srcs, p.nsrcs, p.B, 16)
+                                   : (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 &&
+                                         (p.src_offsets ? p.src_offsets_aligned != 0
+                                                        : (int64_t(p.H) * p.W * p.Cin) % 16 == 0);
+  const bool dst_aligned = p.ndsts ? dsts_ok(p.dsts, p.ndsts, p.B, 16) : (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0;
+  const bool vec = (c.w % PPT) == 0 && (p.W % 4) == 0 && src_aligned && dst_aligned &&
+                   (int64_t(c.h) * c.w * p.Cout * ELEM) % 16 == 0;
+  if (vec && p.Cin == 4) {
+    launch_crop_vec<PPT, 4, OUTT>(p, c, s);
+  } else if (vec && p.Cin == 3) {
+    launch_crop_vec<PPT, 3, OUTT>(p, c, s);
+  } else {
+    const int64_t work = int64_t(p.B) * c.h * c.w;
+    decode_crop_scalar_kernel<OUTT><<<grid_for(work, p.max_grid), kBlock, 0, s>>>(p, c);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t stream) {
+  // every condition is checked here, before anything is launched
+  if (p.B < 0 || p.B > kMaxSrcs || p.H <= 0 || p.W <= 0 || c.h <= 0 || c.w <= 0 || c.h > p.H || c.w > p.W)
+    return hipErrorInvalidValue;
+  for (int b = 0; b < p.B; ++b)
+    if (c.y0[b] < 0 || c.x0[b] < 0 || int(c.y0[b]) + c.h > p.H || int(c.x0[b]) + c.w > p.W) return hipErrorInvalidValue;
+  if (p.Cout < 1 || p.Cout > 4 || p.Cin < 1 || p.Cin > 4) return hipErrorInvalidValue;
+  if (p.nsrcs && (p.nsrcs != p.B || !srcs_ok(p.srcs, p.nsrcs, p.B, 1))) return hipErrorInvalidValue;
+  if (p.ndsts && (p.ndsts != p.B || !dsts_ok(p.dsts, p.ndsts, p.B, 1))) return hipErrorInvalidValue;
+  for (int k = 0; k < p.Cout; ++k)
+    if (p.cmap[k] < 0 || p.cmap[k] >= p.Cin) return hipErrorInvalidValue;
+  if (p.B == 0) return hipSuccess;
+  switch (p.out_dtype) {
+    case OUT_F32: return launch_crop_out<OUT_F32>(p, c, stream);
+    case OUT_BF16: return launch_crop_out<OUT_BF16>(p, c, stream);
+    case OUT_F16: return launch_crop_out<OUT_F16>(p, c, stream);
+    case OUT_U8: return launch_crop_out<OUT_U8>(p, c, stream);
   }
   return hipErrorInvalidValue;
 }

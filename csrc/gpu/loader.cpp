@@ -150,6 +150,15 @@ StreamLoader::StreamLoader(const LoaderConfig& cfg) : cfg_(cfg) {
   if ((cfg_.jitter || !cfg_.matrices.empty()) && cfg_.batch_size > kMaxSrcs)
     throw std::invalid_argument("StreamLoader: per-image colour transforms need batch_size <= 64");
   jit_state_ = cfg_.jitter_seed * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+  if (cfg_.crop) {
+    if (cfg_.color_matrix) throw std::invalid_argument("StreamLoader: a crop does not combine with the colour kernel");
+    if (cfg_.batch_size > kMaxSrcs) throw std::invalid_argument("StreamLoader: a crop needs batch_size <= 64");
+    if (cfg_.crop_h < 1 || cfg_.crop_w < 1 || cfg_.crop_h > INT16_MAX || cfg_.crop_w > INT16_MAX ||
+        cfg_.crop_mode < crop::kRandom || cfg_.crop_mode > crop::kFixed || cfg_.crop_y0 < 0 || cfg_.crop_x0 < 0 ||
+        !(cfg_.mirror >= 0.0 && cfg_.mirror <= 1.0) || (cfg_.x_align != 1 && cfg_.x_align != 4 && cfg_.x_align != 16))
+      throw std::invalid_argument("StreamLoader: bad crop (size >= 1, mirror in [0, 1], x_align 1, 4 or 16)");
+  }
+  crop_state_ = crop::seed_state(cfg_.crop_seed);
   int k = std::max(1, std::min<int>(cfg_.io_threads, int(cfg_.addresses.size())));
   for (int i = 0; i < k; ++i) {
     ctxs_.emplace_back(new zmtp::Context());
@@ -664,9 +673,17 @@ bool StreamLoader::process(zmtp::Message&& msg) {
       if (cfg_.cmap[k] >= c) throw std::runtime_error("StreamLoader: channel map exceeds image channels");
     if (cfg_.color_matrix && (c != 4 || (int64_t(h) * w) % 256 != 0 || w % 4 != 0))
       throw std::runtime_error("StreamLoader: colour matrix needs RGBA input with H*W % 256 == 0, W % 4 == 0");
+    if (cfg_.crop && (!crop::fits(crop_spec(), h, w) || h > INT16_MAX || w > INT16_MAX)) {
+      const std::string at = cfg_.crop_mode == crop::kFixed
+                                 ? " at (" + std::to_string(cfg_.crop_y0) + ", " + std::to_string(cfg_.crop_x0) + ")"
+                                 : std::string();
+      return bad("a " + std::to_string(cfg_.crop_h) + "x" + std::to_string(cfg_.crop_w) + " crop window" + at +
+                 " does not fit the stream's " + std::to_string(h) + "x" + std::to_string(w) + " frames");
+    }
     img_bytes_ = size_t(h) * w * c;
+    // (an identity decode with a crop is no pass-through: it takes the kernel)
     passthrough_ = cfg_.out_dtype == OUT_U8 && cfg_.layout == NHWC && cfg_.cout == c && !cfg_.flip_all &&
-                   !cfg_.color_matrix;
+                   !cfg_.color_matrix && !cfg_.crop;
     for (int k = 0; passthrough_ && k < c; ++k) {
       passthrough_ = cfg_.cmap[k] == k;
       for (int v = 0; passthrough_ && v < 256; ++v) passthrough_ = cfg_.lut[size_t(k) * 256 + size_t(v)] == float(v);
@@ -744,6 +761,10 @@ bool StreamLoader::process(zmtp::Message&& msg) {
       it.jit[k] = lo + (hi - lo) * u;
     }
   }
+  if (cfg_.crop) {
+    if (it.tiled) return bad("tile16 frames cannot be cropped (a crop reads raw or rgb_a frames)");
+    it.win = crop::draw(crop_state_, crop_spec(), h, w);
+  }
   if (cur_.empty()) batch_t0_ = now_ms();
   {
     std::lock_guard<std::mutex> lk(mu_);
@@ -800,6 +821,13 @@ const void* StreamLoader::decoded_key(KeyFrame& kf, bool flip, size_t out_img_by
   dp.layout = cfg_.layout;
   check(decode(dp, stream_), "decode(key frame)");
   return d;
+}
+
+crop::Spec StreamLoader::crop_spec() const {
+  crop::Spec s;
+  s.h = cfg_.crop_h, s.w = cfg_.crop_w, s.mode = cfg_.crop_mode;
+  s.oy = cfg_.crop_y0, s.ox = cfg_.crop_x0, s.mirror = cfg_.mirror, s.x_align = cfg_.x_align;
+  return s;
 }
 
 bool StreamLoader::reads_rgb_only() const {
@@ -1073,7 +1101,8 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   }
   const size_t elem = cfg_.color_matrix ? 4 : (cfg_.out_dtype == OUT_F32 ? 4 : (cfg_.out_dtype == OUT_U8 ? 1 : 2));
   const int cout = cfg_.cout;   // (colour kernel: 4, or 3 for RGB jitter)
-  const size_t out_img_bytes = size_t(H_) * W_ * cout * elem;
+  // (with a crop the output image is the window)
+  const size_t out_img_bytes = cfg_.crop ? size_t(cfg_.crop_h) * cfg_.crop_w * cout * elem : size_t(H_) * W_ * cout * elem;
   uint64_t flips[4] = {0, 0, 0, 0};
   std::vector<const Item*> all;
   all.reserve(size_t(total));
@@ -1235,6 +1264,29 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     std::memcpy(dp.flip_bits, flips, sizeof(flips));
     dp.out_dtype = cfg_.out_dtype;
     dp.layout = cfg_.layout;
+    // crop: the same launches through decode_crop, which reads only each
+    // image's window -- of the host frames (direct) or of the staging buffer
+    // (copy path: just a dense source)
+    CropParams crop;
+    crop.h = cfg_.crop_h, crop.w = cfg_.crop_w;
+    auto set_window = [](CropParams& c, int n, const Item& it) {
+      c.y0[n] = int16_t(it.win.y0), c.x0[n] = int16_t(it.win.x0);
+      if (it.win.m) c.mirror_bits |= uint64_t(1) << n;
+    };
+    if (cfg_.crop) {
+      if (total > kMaxSrcs) throw std::runtime_error("StreamLoader: a crop launch holds at most 64 images");
+      for (int i = 0; i < total; ++i) set_window(crop, i, *all[size_t(i)]);
+      if (direct) {
+        // only the windows cross the link: take back what process() counted for whole frames
+        uint64_t whole = 0, window = 0;
+        for (const Item* it : all) {
+          whole += it->planar ? uint64_t(H_) * W_ * 3 : uint64_t(img_bytes_);
+          window += uint64_t(cfg_.crop_h) * cfg_.crop_w * (it->planar ? 3 : C_);
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        stats_.image_bytes -= whole - window;
+      }
+    }
     if (nplanar > 0 && nplanar < total) {
       // both source layouts in one group (a mixed fleet with inline
       // producers, or the first frames before a producer saw the hint): one
@@ -1242,6 +1294,8 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       for (int pl = 0; pl < 2 && e == hipSuccess; ++pl) {
         DecodeParams sp = dp;
         std::memset(sp.flip_bits, 0, sizeof(sp.flip_bits));
+        CropParams sc;
+        sc.h = crop.h, sc.w = crop.w;
         int n = 0, i = 0;
         for (auto& b : group)
           for (size_t k = 0; k < b.items.size(); ++k, ++i) {
@@ -1250,11 +1304,12 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
             sp.srcs[n] = it.dsrc;
             sp.dsts[n] = static_cast<uint8_t*>(b.dst) + k * out_img_bytes;
             if (it.flip) sp.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
+            if (cfg_.crop) set_window(sc, n, it);
             ++n;
           }
         sp.B = sp.nsrcs = sp.ndsts = n;
         sp.Cin = pl == 1 ? 3 : C_;
-        e = decode(sp, st);
+        e = cfg_.crop ? decode_crop(sp, sc, st) : decode(sp, st);
       }
       // (stats_.launches counts launch groups: this one stays one coalesced
       // launch for the batches in it, run as two kernels)
@@ -1271,7 +1326,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       }
       e = decode_tiles(dp, tp, stream_);
     } else {
-      e = decode(dp, st);
+      e = cfg_.crop ? decode_crop(dp, crop, st) : decode(dp, st);
     }
   }
   check(e, "decode kernel launch");
@@ -1306,6 +1361,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       }
       if (!it.expanded.empty()) fl.expanded.push_back(std::move(it.expanded));
       if (cfg_.jitter) rb.jitter.insert(rb.jitter.end(), it.jit, it.jit + 4);
+      if (cfg_.crop) rb.crop.insert(rb.crop.end(), {it.win.y0, it.win.x0, it.win.m});
       if (it.staged) fl.staged.push_back(std::move(it.staged));
       rb.items.push_back(std::move(it.meta));
     }

@@ -46,6 +46,7 @@
 
 #include "../codec/pickle_codec.h"
 #include "../common/buffer.h"
+#include "../common/crop_draw.h"
 #include "../transport/shmring.h"
 #include "../transport/zmtp.h"
 #include "kernels.h"
@@ -161,6 +162,19 @@ struct LoaderConfig {
   float jitter_range[4] = {0.f, 0.f, 0.f, 0.f};
   float pivot = 0.5f;
   uint64_t jitter_seed = 0;
+  // crop + mirror (kernels.h: decode_crop): every image is decoded through a
+  // crop_h x crop_w window drawn in arrival order (common/crop_draw.h: random
+  // origin and mirror bit from a seeded splitmix64 stream, or the centre, or
+  // the fixed origin); the kernel reads only the window's bytes and the batch
+  // reports the windows it was decoded with.  Not with the colour kernel and
+  // not for tile16 frames.
+  bool crop = false;
+  int crop_h = 0, crop_w = 0;
+  int crop_mode = 0;                 // crop::Mode
+  int crop_y0 = 0, crop_x0 = 0;      // the fixed origin
+  double mirror = 0.0;
+  int x_align = 1;
+  uint64_t crop_seed = 0;
 };
 
 // One delivered batch: metadata of each item (non-image bytes of the frame,
@@ -204,6 +218,7 @@ struct ReadyBatch {
   std::vector<SlotRef> slots;        // host_sync: shm slots re-validated before hand-out
   int64_t launch_no = 0;             // host_sync: the launch that read them
   std::vector<float> jitter;         // colour jitter: 4 factors per image (LoaderConfig::jitter)
+  std::vector<int32_t> crop;         // crop: (y0, x0, mirrored) per image (LoaderConfig::crop)
 };
 
 struct LoaderStats {
@@ -275,6 +290,7 @@ class StreamLoader {
     std::vector<uint8_t> expanded;     // copy path: the frame rebuilt on the host
     BufPtr staged;                     // pinned slot a heap-received image was copied into (direct path)
     float jit[4] = {1.f, 1.f, 1.f, 0.f};   // colour-jitter factors (LoaderConfig::jitter)
+    crop::Window win;                      // crop window (LoaderConfig::crop)
     BatchMeta meta;
   };
   // rebuild on the host what the batch cannot read in place: a key-frame
@@ -331,6 +347,8 @@ class StreamLoader {
   float* d_lut_ = nullptr;
   float* d_mat_ = nullptr;   // 16 matrix + 4 bias (or batch_size x 20: LoaderConfig::matrices)
   uint64_t jit_state_ = 0;   // splitmix64 state of the colour-jitter draws
+  uint64_t crop_state_ = 0;  // splitmix64 state of the crop-window draws
+  crop::Spec crop_spec() const;
   std::vector<Item> cur_;
   std::deque<Pending> pending_;
   int pending_images_ = 0;

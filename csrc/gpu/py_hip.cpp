@@ -243,7 +243,8 @@ PYBIND11_MODULE(_hip, m) {
         [](uintptr_t src, uintptr_t src_offsets, uintptr_t dst, uintptr_t lut, uintptr_t flip, int B, int H, int W,
            int Cin, int Cout, std::vector<int> cmap, int flip_all, int out_dtype, int layout, uintptr_t stream,
            bool src_offsets_aligned, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts,
-           std::vector<uint64_t> flip_bits, int max_grid, int unroll) {
+           std::vector<uint64_t> flip_bits, int max_grid, int unroll, std::vector<int> crop_size,
+           std::vector<int> crop) {
           DecodeParams p;
           fill_image_lists(p, srcs, dsts, flip_bits, "decode");
           p.max_grid = max_grid;
@@ -259,13 +260,31 @@ PYBIND11_MODULE(_hip, m) {
           p.flip_all = flip_all;
           p.out_dtype = out_dtype;
           p.layout = layout;
-          check(decode(p, stream_of(stream)), "decode");
+          if (crop_size.empty()) {
+            check(decode(p, stream_of(stream)), "decode");
+            return;
+          }
+          // a window (crop_size = h, w) of every image: crop = B x (y0, x0, mirrored)
+          if (crop_size.size() != 2 || B < 0 || crop.size() != size_t(B) * 3)
+            throw std::invalid_argument("decode: crop_size is (h, w) and crop holds (y0, x0, mirrored) per image");
+          CropParams c;
+          c.h = crop_size[0], c.w = crop_size[1];
+          if (B <= kMaxSrcs)   // (decode_crop rejects a larger batch)
+            for (int b = 0; b < B; ++b) {
+              const int y0 = crop[size_t(b) * 3], x0 = crop[size_t(b) * 3 + 1];
+              if (y0 < INT16_MIN || y0 > INT16_MAX || x0 < INT16_MIN || x0 > INT16_MAX)
+                throw std::invalid_argument("decode: crop origin out of range");
+              c.y0[b] = int16_t(y0), c.x0[b] = int16_t(x0);
+              if (crop[size_t(b) * 3 + 2]) c.mirror_bits |= uint64_t(1) << b;
+            }
+          check(decode_crop(p, c, stream_of(stream)), "decode_crop");
         },
         py::arg("src"), py::arg("src_offsets"), py::arg("dst"), py::arg("lut"), py::arg("flip"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"),
         py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("src_offsets_aligned") = false,
         py::arg("srcs") = std::vector<uintptr_t>(), py::arg("dsts") = std::vector<uintptr_t>(),
-        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0, py::arg("unroll") = 0);
+        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0, py::arg("unroll") = 0,
+        py::arg("crop_size") = std::vector<int>(), py::arg("crop") = std::vector<int>());
 
   // Key-frame delta decode (kernels.h: decode_tiles) at the pointer level: srcs[b] the encoded frame,
   // fills[b] image b's decoded key frame, tile_start the prefix sums of the payload tile counts.
@@ -1230,7 +1249,8 @@ PYBIND11_MODULE(_hip, m) {
                        int out_dtype, int layout, std::vector<float> lut, std::vector<float> matrix,
                        std::vector<float> bias, bool direct, int launch_depth, int copy_streams, bool host_sync,
                        std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed,
-                       bool planar_alpha, int decode_streams) {
+                       bool planar_alpha, int decode_streams, std::vector<int> crop, const std::string& crop_mode,
+                       std::vector<int> crop_origin, double mirror, int x_align, uint64_t crop_seed) {
              LoaderConfig c;
              c.direct = direct;
              c.decode_streams = decode_streams;
@@ -1269,6 +1289,23 @@ PYBIND11_MODULE(_hip, m) {
                c.pivot = jitter[4];
                c.jitter_seed = jitter_seed;
              }
+             // crop + mirror: crop = (h, w); mode 'random' | 'center', or 'fixed' with crop_origin = (y0, x0)
+             if (!crop.empty()) {
+               if (crop.size() != 2) throw std::invalid_argument("StreamLoader: crop = (h, w)");
+               c.crop = true;
+               c.crop_h = crop[0], c.crop_w = crop[1];
+               if (crop_mode == "random") c.crop_mode = btn::crop::kRandom;
+               else if (crop_mode == "center") c.crop_mode = btn::crop::kCenter;
+               else if (crop_mode == "fixed") c.crop_mode = btn::crop::kFixed;
+               else throw std::invalid_argument("StreamLoader: crop_mode must be 'random', 'center' or 'fixed'");
+               if (c.crop_mode == btn::crop::kFixed) {
+                 if (crop_origin.size() != 2) throw std::invalid_argument("StreamLoader: crop_origin = (y0, x0)");
+                 c.crop_y0 = crop_origin[0], c.crop_x0 = crop_origin[1];
+               }
+               c.mirror = mirror;
+               c.x_align = x_align;
+               c.crop_seed = crop_seed;
+             }
              return new StreamLoader(c);
            }),
            py::arg("addresses"), py::arg("batch_size"), py::arg("image_key"), py::arg("rcvhwm"),
@@ -1278,7 +1315,9 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("bias"), py::arg("direct") = true, py::arg("launch_depth") = 2,
            py::arg("copy_streams") = 2, py::arg("host_sync") = true, py::arg("matrices") = std::vector<float>(),
            py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0, py::arg("planar_alpha") = true,
-           py::arg("decode_streams") = 1)
+           py::arg("decode_streams") = 1, py::arg("crop") = std::vector<int>(), py::arg("crop_mode") = "random",
+           py::arg("crop_origin") = std::vector<int>(), py::arg("mirror") = 0.0, py::arg("x_align") = 1,
+           py::arg("crop_seed") = 0)
       .def("start", &StreamLoader::start)
       .def("wait_shape",
            [](StreamLoader& l, long timeout_ms) -> py::object {
@@ -1329,6 +1368,11 @@ PYBIND11_MODULE(_hip, m) {
                py::array_t<float> f({py::ssize_t(rb.jitter.size() / 4), py::ssize_t(4)});
                std::memcpy(f.mutable_data(), rb.jitter.data(), rb.jitter.size() * sizeof(float));
                meta["color_jitter"] = f;
+             }
+             if (!rb.crop.empty()) {     // the window (y0, x0, mirrored) each image was decoded through
+               py::array_t<int32_t> w({py::ssize_t(rb.crop.size() / 3), py::ssize_t(3)});
+               std::memcpy(w.mutable_data(), rb.crop.data(), rb.crop.size() * sizeof(int32_t));
+               meta["crop"] = w;
              }
              return py::make_tuple(rb.index, meta, rb.recv_ms);
            })

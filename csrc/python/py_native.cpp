@@ -9,6 +9,7 @@
 
 #include "../codec/pickle_codec.h"
 #include "../codec/xform_fit.h"
+#include "../common/crop_draw.h"
 #include "../common/planar_alpha.h"
 #include "../sim/physics.h"
 #include "../sim/raster.h"
@@ -315,6 +316,34 @@ class NativeError(Exception):
     c.op = op, c.a = a, c.b = b, c.d = d, c.r = r;
     return codec::apply_channel(c, x);
   });
+  // the crop windows the stream loader draws for its first n images
+  // (common/crop_draw.h): int32 [n, 3] of (y0, x0, mirrored)
+  m.def("crop_draw",
+        [](uint64_t seed, int H, int W, int h, int w, double mirror, int x_align, const std::string& mode, int n,
+           std::pair<int, int> origin) {
+          crop::Spec s;
+          s.h = h, s.w = w, s.mirror = mirror, s.x_align = x_align;
+          s.oy = origin.first, s.ox = origin.second;
+          if (mode == "random") s.mode = crop::kRandom;
+          else if (mode == "center") s.mode = crop::kCenter;
+          else if (mode == "fixed") s.mode = crop::kFixed;
+          else throw std::invalid_argument("crop_draw: mode must be 'random', 'center' or 'fixed'");
+          if (n < 0 || !(mirror >= 0.0 && mirror <= 1.0)) throw std::invalid_argument("crop_draw: bad n or mirror");
+          if (!crop::fits(s, H, W))
+            throw std::invalid_argument("crop_draw: a " + std::to_string(h) + "x" + std::to_string(w) +
+                                        " window does not fit a " + std::to_string(H) + "x" + std::to_string(W) +
+                                        " frame");
+          py::array_t<int32_t> out({py::ssize_t(n), py::ssize_t(3)});
+          int32_t* o = out.mutable_data();
+          uint64_t state = crop::seed_state(seed);
+          for (int i = 0; i < n; ++i) {
+            const crop::Window win = crop::draw(state, s, H, W);
+            o[3 * i] = win.y0, o[3 * i + 1] = win.x0, o[3 * i + 2] = win.m;
+          }
+          return out;
+        },
+        py::arg("seed"), py::arg("H"), py::arg("W"), py::arg("h"), py::arg("w"), py::arg("mirror"),
+        py::arg("x_align"), py::arg("mode"), py::arg("n"), py::arg("origin") = std::pair<int, int>(0, 0));
   m.def("btr_header", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> offs) {
     std::vector<int64_t> o(offs.data(), offs.data() + offs.size());
     auto h = codec::btr_header(o);

@@ -65,7 +65,8 @@ class DeviceLoader:
         Items per batch (B).
     decode: DecodeConfig
         What the decode kernel does (channels, gamma, normalisation, dtype,
-        layout, flip, optional colour matrix).
+        layout, flip, optional colour matrix or jitter, optional crop +
+        mirror: ``batch['crop']`` then reports each image's window).
     device: torch.device / int / str
         Target GPU (default: current device).
     max_items: int, optional
@@ -251,13 +252,19 @@ class DeviceLoader:
             j = cfg.color_jitter
             jitter = [j.brightness, j.contrast, j.saturation, j.hue, cfg.jitter_pivot]
             seed = int(j.seed) & ((1 << 64) - 1)
+        # crop + mirror inside the decode: windows drawn per image in the loader (batch['crop'])
+        crop = {}
+        if cfg.crop is not None:
+            c = cfg.crop
+            crop = dict(crop=list(c.size), crop_mode=c.kind, crop_origin=list(c.origin or ()), mirror=c.mirror,
+                        x_align=c.x_align, crop_seed=c.seed & ((1 << 64) - 1))
         max_batches = -1 if self.max_items is None else self.max_items // self.batch_size
         return ext.StreamLoader(
             self.addresses, self.batch_size, self.image_key, self.rcvhwm, self.io_threads, self.device.index,
             max_batches, 0, 0, self.staging_depth, self.skip_bad, cfg.cout, list(cfg.cmap) + [0] * (4 - len(cfg.cmap)),
             int(cfg.flip), ops.OUT_DTYPES[cfg.dtype], ops.LAYOUTS[cfg.layout], lut, matrix, bias,
             self.h2d == 'auto', self.launch_depth, self.copy_streams, self.host_sync, matrices, jitter, seed,
-            self.shm_alpha == 'auto', self.decode_streams)
+            self.shm_alpha == 'auto', self.decode_streams, **crop)
 
     def _post(self, loader, stream):
         shape = self.decode.out_shape(self.batch_size, *self.shape[:2])

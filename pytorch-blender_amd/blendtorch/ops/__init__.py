@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 __all__ = [
-    'DecodeConfig', 'ColorJitter', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
+    'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
     'color4x4',
     'project', 'adaptive_avg_pool_nhwc', 'AdaptiveAvgPool2d', 'batch_norm_leaky_relu', 'BatchNormLeakyReLU2d',
     'reference_decode', 'reference_color4x4', 'reference_project', 'reference_gamma',
@@ -140,6 +140,148 @@ def jitter_factors(seed: int, ranges, n: int) -> np.ndarray:
     return out
 
 
+@dataclasses.dataclass(frozen=True)
+class Crop:
+    """Crop (and mirror) inside the fused decode: only the window is read.
+
+    Every image is decoded through an ``h x w`` window of the upright frame,
+    optionally mirrored left-right.  With ``full[b]`` the plain decode of
+    image b and ``(y0, x0, m)`` its window::
+
+        out[b, c, i, j] = full[b, c, y0 + i, x0 + (w - 1 - j if m else j)]
+
+    The kernel reads just the window's rows and columns of the source frame
+    in place (``h*w / (H*W)`` of the bytes over PCIe on the loader's direct
+    path); the values are bit-identical to the plain decode's.
+
+    size: ``(h, w)``.
+    mode: ``'random'`` (default): origin and mirror bit drawn per image from
+        a seeded stream in arrival order (:func:`crop_windows`);
+        ``'center'``: the centred window, never mirrored.
+    origin: ``(y0, x0)``: a fixed window, never mirrored (``mode`` is ignored).
+    mirror: probability of a mirrored window, in [0, 1] (random mode only).
+    seed: seed of the stream (seeded like the colour jitter's: the streams of
+        seeds s and s + 1 are the same draws one apart, so independent
+        streams want seeds far apart).
+    x_align: 1, 4 or 16 -- drawn and centred ``x0`` are multiples of it
+        (source addresses of RGBA frames then share that many pixels'
+        alignment).
+
+    The stream loader reports each batch's windows as ``batch['crop']``
+    (int32 [B, 3]: y0, x0, mirrored) and does not touch the metadata:
+    :func:`crop_points` maps pixel coordinates into the window.  The
+    reference has no such stage.
+    """
+    size: Sequence[int]
+    mode: str = 'random'
+    origin: Optional[Sequence[int]] = None
+    mirror: float = 0.0
+    seed: int = 0
+    x_align: int = 1
+
+    def __post_init__(self):
+        try:
+            size = tuple(int(v) for v in self.size)
+        except TypeError:
+            raise ValueError('Crop.size must be (h, w)') from None
+        if len(size) != 2 or size[0] < 1 or size[1] < 1 or max(size) > 32767:
+            raise ValueError('Crop.size must be (h, w) with 1 <= h, w <= 32767')
+        object.__setattr__(self, 'size', size)
+        if self.mode not in ('random', 'center'):
+            raise ValueError("Crop.mode must be 'random' or 'center'")
+        if self.origin is not None:
+            origin = tuple(int(v) for v in self.origin)
+            if len(origin) != 2 or origin[0] < 0 or origin[1] < 0 or max(origin) > 32767:
+                raise ValueError('Crop.origin must be (y0, x0) with 0 <= y0, x0 <= 32767')
+            object.__setattr__(self, 'origin', origin)
+        if not 0.0 <= float(self.mirror) <= 1.0:
+            raise ValueError('Crop.mirror must be a probability in [0, 1]')
+        object.__setattr__(self, 'mirror', float(self.mirror))
+        if self.mirror and self.kind != 'random':
+            raise ValueError("Crop.mirror is drawn per image: it needs mode 'random' and no fixed origin")
+        if self.x_align not in (1, 4, 16):
+            raise ValueError('Crop.x_align must be 1, 4 or 16')
+        object.__setattr__(self, 'seed', int(self.seed))
+
+    @property
+    def kind(self):
+        """'fixed' with an origin, else the mode."""
+        return 'fixed' if self.origin is not None else self.mode
+
+    def check_frame(self, H, W):
+        """ValueError unless the window lies inside an H x W frame."""
+        h, w = self.size
+        y0, x0 = self.origin if self.origin is not None else (0, 0)
+        if y0 + h > H or x0 + w > W:
+            at = f' at {self.origin}' if self.origin is not None else ''
+            raise ValueError(f'a {h}x{w} crop window{at} does not fit a {H}x{W} frame')
+
+
+def crop_windows(crop: Crop, H: int, W: int, n: int) -> np.ndarray:
+    """int32 [n, 3]: the windows (y0, x0, mirrored) the stream loader gives
+    its first ``n`` images of H x W frames (csrc/common/crop_draw.h;
+    ``_native.crop_draw`` is the same function natively).  Random mode draws
+    three splitmix64 words z per image, in integer arithmetic only:
+    ``y0 = ((z >> 32) * (H - h + 1)) >> 32``,
+    ``x0 = (((z >> 32) * ((W - w) // x_align + 1)) >> 32) * x_align``,
+    ``m = (z >> 40) < int(mirror * 2**24)``."""
+    crop.check_frame(H, W)
+    h, w = crop.size
+    out = np.zeros((n, 3), np.int32)
+    if crop.kind == 'fixed':
+        out[:, 0], out[:, 1] = crop.origin
+        return out
+    a = crop.x_align
+    if crop.kind == 'center':
+        out[:, 0] = (H - h) // 2
+        out[:, 1] = (W - w) // 2 // a * a
+        return out
+    M64 = (1 << 64) - 1
+    state = (crop.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & M64
+
+    def draw():
+        nonlocal state
+        state = (state + 0x9E3779B97F4A7C15) & M64
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+        return z ^ (z >> 31)
+    thresh = int(crop.mirror * 16777216.0)
+    for i in range(n):
+        out[i, 0] = ((draw() >> 32) * (H - h + 1)) >> 32
+        out[i, 1] = (((draw() >> 32) * ((W - w) // a + 1)) >> 32) * a
+        out[i, 2] = (draw() >> 40) < thresh
+    return out
+
+
+def crop_points(xy, crop, size):
+    """Map pixel coordinates of the full frame into crop windows.
+
+    xy: numpy array or torch tensor [B, ..., 2] of (x, y); crop: the [B, 3]
+    windows (``batch['crop']``); size: the window's (h, w).  Returns
+    ``x' = x - x0`` (``w - 1 - (x - x0)`` for a mirrored window) and
+    ``y' = y - y0``, as the type of ``xy``.  Points outside the window keep
+    coordinates outside ``[0, w) x [0, h)``."""
+    w = int(size[1])
+    is_np = isinstance(xy, np.ndarray) or not hasattr(xy, 'new_tensor')
+    if is_np:
+        xy = np.asarray(xy)
+        win = np.asarray(crop).reshape(-1, 3).astype(xy.dtype)
+        where, stack = np.where, np.stack
+    else:
+        import torch
+        win = torch.as_tensor(np.asarray(crop) if not isinstance(crop, torch.Tensor) else crop).reshape(-1, 3)
+        win = win.to(device=xy.device, dtype=xy.dtype)
+        where, stack = torch.where, torch.stack
+    if xy.shape[0] != win.shape[0] or xy.shape[-1] != 2:
+        raise ValueError('crop_points: xy is [B, ..., 2] with one window per leading index')
+    shape = (win.shape[0],) + (1,) * (xy.ndim - 2)
+    y0, x0, m = (win[:, k].reshape(shape) for k in range(3))
+    x = xy[..., 0] - x0
+    x = where(m != 0, (w - 1) - x, x)
+    return stack([x, xy[..., 1] - y0], -1)
+
+
 _LUMA = np.array([0.213, 0.715, 0.072])
 
 
@@ -186,6 +328,9 @@ class DecodeConfig:
     color_jitter: a :class:`ColorJitter` -- a random transform per image,
         built inside the same kernel, applied to ``gamma(x) * scale``
         (channels 'rgb' or 'rgba', no mean/std).
+    crop: a :class:`Crop` -- every image is decoded through a window (and
+        optionally mirrored); the output has the window's size.  Not with the
+        colour-kernel options (color_matrix, color_matrices, color_jitter).
     """
     channels: object = 'rgb'
     gamma: Optional[float] = None
@@ -200,6 +345,7 @@ class DecodeConfig:
     color_matrices: Optional[Sequence] = None
     color_biases: Optional[Sequence] = None
     color_jitter: Optional[ColorJitter] = None
+    crop: Optional[Crop] = None
 
     def __post_init__(self):
         # normalise sequences to tuples: configs are hashable cache keys
@@ -243,6 +389,11 @@ class DecodeConfig:
         if (self.color_matrices is not None or self.color_jitter is not None) and \
                 (self.dtype != 'float32' or self.layout != 'nchw'):
             raise ValueError('per-image colour transforms produce float32 NCHW output')
+        if self.crop is not None:
+            if not isinstance(self.crop, Crop):
+                raise TypeError('crop must be an ops.Crop')
+            if self.colour_kernel:
+                raise ValueError('crop does not combine with color_matrix, color_matrices or color_jitter')
 
     # -- presets -----------------------------------------------------------
     @classmethod
@@ -285,7 +436,12 @@ class DecodeConfig:
         return float(j.pivot) if j is not None and j.pivot is not None else 127.5 * float(self.scale)
 
     def out_shape(self, B, H, W):
+        """Shape of B decoded H x W frames (with a crop: B windows; ValueError
+        when the window does not fit the frame)."""
         c = self.cout
+        if self.crop is not None:
+            self.crop.check_frame(H, W)
+            H, W = self.crop.size
         return (B, c, H, W) if self.layout == 'nchw' else (B, H, W, c)
 
     def torch_dtype(self):
@@ -431,11 +587,39 @@ def reference_gamma(images, gamma):
     return rgb
 
 
-def reference_decode(images, cfg: DecodeConfig, flip=None, jitter=None):
+def _crop_rows(crop, B):
+    """The [B, 3] windows as a list of int triples."""
+    if crop is None:
+        raise ValueError('a crop config needs the batch\'s windows: crop=[B, 3] of (y0, x0, mirrored)')
+    if hasattr(crop, 'detach'):
+        crop = crop.detach().cpu().numpy()
+    win = np.asarray(crop)
+    if win.shape != (B, 3):
+        raise ValueError(f'crop must be [{B}, 3] (y0, x0, mirrored), not {list(win.shape)}')
+    return [tuple(int(v) for v in r) for r in win]
+
+
+def reference_decode(images, cfg: DecodeConfig, flip=None, jitter=None, crop=None):
     """fp32 PyTorch reference of :func:`decode` (images: u8 [B,H,W,C]); for a
     ``color_jitter`` config, ``jitter`` holds the [B, 4] factors of the batch
-    (``batch['color_jitter']``)."""
+    (``batch['color_jitter']``); for a ``crop`` config, ``crop`` holds its
+    [B, 3] windows (``batch['crop']``): the uncropped reference, sliced and
+    mirrored."""
     import torch
+    if cfg.crop is not None:
+        full = reference_decode(images, dataclasses.replace(cfg, crop=None), flip=flip, jitter=jitter)
+        h, w = cfg.crop.size
+        ya, xa = (2, 3) if cfg.layout == 'nchw' else (1, 2)
+        cfg.crop.check_frame(full.shape[ya], full.shape[xa])
+        outs = []
+        for b, (y0, x0, m) in enumerate(_crop_rows(crop, full.shape[0])):
+            if y0 < 0 or x0 < 0 or y0 + h > full.shape[ya] or x0 + w > full.shape[xa]:
+                raise ValueError(f'crop window {(y0, x0)} + {(h, w)} leaves the frame')
+            o = full[b].narrow(ya - 1, y0, h).narrow(xa - 1, x0, w)
+            outs.append(torch.flip(o, dims=[xa - 1]) if m else o)
+        return torch.stack(outs)
+    if crop is not None:
+        raise ValueError('crop windows given for a config without a crop')
     x = images
     if x.dim() == 3:
         x = x.unsqueeze(-1)
@@ -550,8 +734,10 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None):
-    """Fused decode of a u8 [B,H,W,C] device tensor with the gfx950 kernel."""
+def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None, crop=None):
+    """Fused decode of a u8 [B,H,W,C] device tensor with the gfx950 kernel.
+    For a ``crop`` config, ``crop`` holds the [B, 3] windows (y0, x0,
+    mirrored) of the batch, e.g. from :func:`crop_windows` (B <= 64)."""
     import torch
     ext = hip_ext()
     if images.dtype != torch.uint8 or not images.is_cuda:
@@ -580,8 +766,17 @@ def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None):
         if fl_t.numel() != B:
             raise ValueError('flip needs one flag per image')
         fl = fl_t.data_ptr()
+    kw = {}
+    if cfg.crop is not None:
+        if B > 64:
+            raise ValueError('decode: a crop config takes at most 64 images per call')
+        if tuple(out.shape) != tuple(cfg.out_shape(B, H, W)) or not out.is_contiguous():
+            raise ValueError('decode: out must be a contiguous tensor of the window\'s shape')
+        kw = dict(crop_size=list(cfg.crop.size), crop=[v for r in _crop_rows(crop, B) for v in r])
+    elif crop is not None:
+        raise ValueError('crop windows given for a config without a crop')
     ext.decode(x.data_ptr(), 0, out.data_ptr(), lut.data_ptr(), fl, B, H, W, C, cfg.cout, cfg.cmap,
-               int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], _stream(x.device))
+               int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], _stream(x.device), **kw)
     return out
 
 
@@ -596,6 +791,8 @@ def decode_gather(store, index, cfg: DecodeConfig = DecodeConfig(), out=None):
         raise TypeError('decode_gather expects a contiguous uint8 [N,H,W,C] CUDA/HIP tensor')
     if cfg.colour_kernel:
         raise ValueError('decode_gather: colour matrices are not supported; use color4x4 on store[index]')
+    if cfg.crop is not None:
+        raise ValueError('decode_gather: crops are not supported; use decode(store[index], cfg, crop=windows)')
     N, H, W, C = store.shape
     if max(cfg.cmap) >= C:
         raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
@@ -650,6 +847,8 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
         raise TypeError('replay_sample expects a contiguous uint8 [N,H,W,C] device tensor')
     if cfg.colour_kernel:
         raise ValueError('replay_sample does not apply colour matrices (use gather + color4x4)')
+    if cfg.crop is not None:
+        raise ValueError('replay_sample does not crop (use decode(store[index], cfg, crop=windows))')
     N, H, W, C = store.shape
     if max(cfg.cmap) >= C:
         raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
@@ -1523,8 +1722,8 @@ def decode_lut_bf16(cfg: DecodeConfig, device):
     through (``conv4x4s2(..., lut=)``) -- the same values the decode kernel
     writes for a bf16 NHWC RGBA output.  Cached per (config, device)."""
     import torch
-    if cfg.cmap != [0, 1, 2, 3] or cfg.flip or cfg.colour_kernel:
-        raise ValueError('decode_lut_bf16: RGBA identity channel map, no flip, no colour matrix')
+    if cfg.cmap != [0, 1, 2, 3] or cfg.flip or cfg.colour_kernel or cfg.crop is not None:
+        raise ValueError('decode_lut_bf16: RGBA identity channel map, no flip, no colour matrix, no crop')
     key = (cfg, str(device))
     t = _LUTS.get(key)
     if t is None:
