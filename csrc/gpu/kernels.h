@@ -106,6 +106,27 @@ struct CropParams {
 };
 hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t stream);
 
+// decode() of per-image sources (p.nsrcs == p.B <= kMaxSrcs, usually host
+// memory) of which only a region is read: image b's bytes in stored rows
+// [y0[b], y1[b]] x pixel columns [x0[b], x1[b]] (inclusive; y1 < y0: none)
+// come from p.srcs[b] and are also written, raw, to the same offsets of
+// mirror[b]; every other byte of the frame comes from mirror[b], a device
+// copy of H * W * Cin bytes that already holds it (slot_mirror.h).  After the
+// launch mirror[b] equals the frame.  mirror[b] == nullptr: the whole image
+// is read from p.srcs[b] and nothing is stored.  Values are bit-identical to
+// decode()'s.  Only the vector path exists: Cin 3 or 4, W a multiple of the
+// lane's pixel group, H * W * Cin % 16 == 0, sources, mirrors and outputs
+// 16-byte aligned; x0[b] and x1[b] + 1 multiples of 64 (x1[b] may be W - 1),
+// or the region spans full rows.  Anything else is hipErrorInvalidValue,
+// checked on the host: nothing is launched.  p.unroll is ignored.
+struct DeltaParams {
+  uint8_t* mirror[kMaxSrcs] = {};
+  int16_t y0[kMaxSrcs] = {}, y1[kMaxSrcs] = {}, x0[kMaxSrcs] = {}, x1[kMaxSrcs] = {};
+};
+// the launch-wide conditions above (everything but the regions themselves)
+bool decode_delta_supported(const DecodeParams& p);
+hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t stream);
+
 // Key-frame delta frames (csrc/codec/tiledelta.h), decoded in two launches
 // on `stream` with the same table, channel map, dtype and layout as decode():
 //   1. output image b <- fills[b]: its producer's key frame, already decoded

@@ -646,6 +646,64 @@ __global__ __launch_bounds__(kBlock) void decode_crop_scalar_kernel(DecodeParams
   }
 }
 
+// ---- region read + slot mirror (kernels.h: decode_delta) -------------------
+// decode_vec_kernel's groups, table, lookup and stores; only the source of a
+// lane's one load differs.  A region starts and ends on multiples of 64
+// pixels (or spans full rows) and a group is PPT <= 16 pixels of one row with
+// W % PPT == 0, so a group lies inside or outside the region as a whole: the
+// base pointer is selected, never branched on, and the load is issued once.
+
+// Store PPT pixels back (the widths load_pixels reads them with).
+template <int PPT, int CIN>
+__device__ __forceinline__ void store_pixels(uint8_t* p, const Pixels<PPT, CIN>& px) {
+  constexpr int NB = PPT * CIN;
+  if constexpr (NB % 16 == 0) {
+#pragma unroll
+    for (int i = 0; i < NB / 16; ++i)
+      reinterpret_cast<uint4*>(p)[i] = make_uint4(px.w[4 * i], px.w[4 * i + 1], px.w[4 * i + 2], px.w[4 * i + 3]);
+  } else if constexpr (NB % 8 == 0) {
+#pragma unroll
+    for (int i = 0; i < NB / 8; ++i) reinterpret_cast<uint2*>(p)[i] = make_uint2(px.w[2 * i], px.w[2 * i + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NB / 4; ++i) reinterpret_cast<uint32_t*>(p)[i] = px.w[i];
+  }
+}
+
+template <int PPT, int CIN, int OUTT, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void decode_delta_kernel(DecodeParams p, DeltaParams d) {
+  __shared__ uint32_t tab[kTabWords];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  __syncthreads();
+
+  const int64_t HW = int64_t(p.H) * p.W;
+  const int64_t groups_per_img = HW / PPT;
+  const int64_t total = groups_per_img * p.B;
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) cm[c] = p.cmap[c];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  const bool small = total + stride < (int64_t(1) << 31) && HW < (int64_t(1) << 31);
+
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += stride) {
+    Group gr;
+    int y, x;
+    split_group<PPT>(g, groups_per_img, p.W, small, gr.b, gr.q, y, x);
+    const int b = gr.b;
+    const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
+    const int64_t off = (int64_t(sy) * p.W + x) * CIN;
+    uint8_t* mir = d.mirror[b];
+    const bool inside = mir == nullptr || (sy >= int(d.y0[b]) && sy <= int(d.y1[b]) && x >= int(d.x0[b]) && x <= int(d.x1[b]));
+    const uint8_t* base = inside ? p.srcs[b] : mir;
+    gr.src = base + off;
+    Pixels<PPT, CIN> px;
+    load_pixels<PPT, CIN>(gr.src, px);
+    if (inside && mir != nullptr) store_pixels<PPT, CIN>(mir + off, px);
+    emit<PPT, CIN, OUTT, LAYOUT>(p, xf, cm, cout, HW, gr, px);
+  }
+}
+
 int grid_for(int64_t work, int cap = 0) {
   // Measured on MI355X (profiles/decode_unroll_sweep.txt): up to ~4k blocks
   // of work, one resident wave of 2048 blocks (256 CUs x 8) is best; for
@@ -814,6 +872,63 @@ hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t s
     case OUT_BF16: return launch_crop_out<OUT_BF16>(p, c, stream);
     case OUT_F16: return launch_crop_out<OUT_F16>(p, c, stream);
     case OUT_U8: return launch_crop_out<OUT_U8>(p, c, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+namespace {
+
+constexpr int delta_ppt(int out_dtype) { return out_dtype == OUT_F32 ? 4 : (out_dtype == OUT_U8 ? 16 : 8); }
+
+template <int OUTT>
+hipError_t launch_delta_out(const DecodeParams& p, const DeltaParams& d, hipStream_t s) {
+  constexpr int PPT = delta_ppt(OUTT);
+  const int grid = grid_for(int64_t(p.B) * p.H * p.W / PPT, p.max_grid);
+  if (p.Cin == 4) {
+    if (p.layout == NCHW) decode_delta_kernel<PPT, 4, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_delta_kernel<PPT, 4, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+  } else {
+    if (p.layout == NCHW) decode_delta_kernel<PPT, 3, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_delta_kernel<PPT, 3, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+bool decode_delta_supported(const DecodeParams& p) {
+  if (p.B < 1 || p.B > kMaxSrcs || p.nsrcs != p.B || p.H <= 0 || p.W <= 0 || p.H > INT16_MAX || p.W > INT16_MAX)
+    return false;
+  if ((p.Cin != 3 && p.Cin != 4) || p.Cout < 1 || p.Cout > 4) return false;
+  if (p.out_dtype < OUT_F32 || p.out_dtype > OUT_U8 || (p.layout != NCHW && p.layout != NHWC)) return false;
+  for (int c = 0; c < p.Cout; ++c)
+    if (p.cmap[c] < 0 || p.cmap[c] >= p.Cin) return false;
+  if (p.W % delta_ppt(p.out_dtype) != 0 || (int64_t(p.H) * p.W * p.Cin) % 16 != 0) return false;
+  if (!srcs_ok(p.srcs, p.nsrcs, p.B, 16)) return false;
+  return p.ndsts ? dsts_ok(p.dsts, p.ndsts, p.B, 16) : p.dst != nullptr && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0;
+}
+
+hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t stream) {
+  // every condition is checked here, before anything is launched
+  if (p.B == 0) return hipSuccess;
+  if (!decode_delta_supported(p)) return hipErrorInvalidValue;
+  const size_t elem = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 1 : 2);
+  if (!p.ndsts && (size_t(p.H) * p.W * p.Cout * elem) % 16 != 0) return hipErrorInvalidValue;
+  for (int b = 0; b < p.B; ++b) {
+    if (!d.mirror[b]) continue;
+    if ((reinterpret_cast<uintptr_t>(d.mirror[b]) % 16) != 0) return hipErrorInvalidValue;
+    const int y0 = d.y0[b], y1 = d.y1[b], x0 = d.x0[b], x1 = d.x1[b];
+    if (y1 < y0) continue;   // nothing from the host
+    if (y0 < 0 || y1 >= p.H || x0 < 0 || x1 < x0 || x1 >= p.W) return hipErrorInvalidValue;
+    const bool full_rows = x0 == 0 && x1 == p.W - 1;
+    const bool blocks = x0 % 64 == 0 && ((x1 + 1) % 64 == 0 || x1 == p.W - 1) && p.W % 64 == 0;
+    if (!full_rows && !blocks) return hipErrorInvalidValue;
+  }
+  switch (p.out_dtype) {
+    case OUT_F32: return launch_delta_out<OUT_F32>(p, d, stream);
+    case OUT_BF16: return launch_delta_out<OUT_BF16>(p, d, stream);
+    case OUT_F16: return launch_delta_out<OUT_F16>(p, d, stream);
+    case OUT_U8: return launch_delta_out<OUT_U8>(p, d, stream);
   }
   return hipErrorInvalidValue;
 }

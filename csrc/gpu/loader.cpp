@@ -159,6 +159,7 @@ StreamLoader::StreamLoader(const LoaderConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("StreamLoader: bad crop (size >= 1, mirror in [0, 1], x_align 1, 4 or 16)");
   }
   crop_state_ = crop::seed_state(cfg_.crop_seed);
+  mirror_budget_ = mirror::Budget(cfg_.slot_mirror_max_bytes);
   int k = std::max(1, std::min<int>(cfg_.io_threads, int(cfg_.addresses.size())));
   for (int i = 0; i < k; ++i) {
     ctxs_.emplace_back(new zmtp::Context());
@@ -302,9 +303,13 @@ void StreamLoader::promote_ready() {
     // a launch reap() has retired was validated there (before its slots were
     // handed back: they may already belong to new frames); otherwise the
     // slots are still held by this loader and are checked here
-    const bool torn = rb.launch_no > retired_launch_ &&
-                      std::any_of(rb.slots.begin(), rb.slots.end(),
-                                  [](const ReadyBatch::SlotRef& s) { return !s.seg->valid(s.slot, s.gen); });
+    bool torn = false;
+    if (rb.launch_no > retired_launch_)
+      for (const ReadyBatch::SlotRef& s : rb.slots)
+        if (!s.seg->valid(s.slot, s.gen)) {
+          torn = true;
+          invalidate_mirror(s.seg, s.slot);   // its mirror copy may hold the next frame's bytes
+        }
     std::lock_guard<std::mutex> lk(mu_);
     if ((torn || !error_.empty()) && !cfg_.skip_bad) {   // reap() may have failed the stream already
       if (error_.empty())
@@ -370,7 +375,11 @@ void StreamLoader::stop() {
   }
   pending_.clear();
   pending_images_ = 0;
-  for (auto& kv : segments_) (void)hipHostUnregister(kv.second.seg->base());
+  for (auto& kv : segments_) {
+    (void)hipHostUnregister(kv.second.seg->base());
+    if (kv.second.mirror_dev) (void)hipFree(kv.second.mirror_dev);
+  }
+  by_seg_.clear();
   segments_.clear();
   for (auto& kv : keys_) {
     if (kv.second.dev) (void)hipFree(kv.second.dev);
@@ -583,6 +592,7 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     try {
       MappedSegment& ms = segment(d.items[0]->s);
       it.seg = ms.seg.get();
+      it.ms = &ms;
       dev_base = ms.dev_base;
     } catch (const std::exception& e) {
       return bad(e.what());
@@ -605,6 +615,23 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     guard.armed = true;   // claimed: every exit but the hand-over to cur_ gives it back
     it.src = it.seg->base() + off;
     if (dev_base) it.dsrc = dev_base + off;
+    if (d.items.size() >= 10 && d.items[9]->kind == codec::Value::TUPLE) {
+      // 10th element (base_gen, y0, y1, x0, x1): all of the frame outside the
+      // rectangle is what this slot held at generation base_gen (shmring.h)
+      const codec::Value& dv = *d.items[9];
+      bool ok = dv.items.size() == 5;
+      for (size_t k = 0; ok && k < 5; ++k) ok = dv.items[k]->kind == codec::Value::INT;
+      const int64_t lim = int64_t(1) << 20;
+      for (size_t k = 1; ok && k < 5; ++k) ok = dv.items[k]->i >= -lim && dv.items[k]->i <= lim;
+      if (ok) {
+        it.delta.base_gen = uint32_t(dv.items[0]->i);
+        it.delta.rect.y0 = int(dv.items[1]->i), it.delta.rect.y1 = int(dv.items[2]->i);
+        it.delta.rect.x0 = int(dv.items[3]->i), it.delta.rect.x1 = int(dv.items[4]->i);
+        ok = mirror::delta_valid(it.delta, h, w);
+      }
+      if (!ok) return bad("malformed _btshm delta");
+      it.has_delta = !has_codec || (d.items[8]->items.size() == 1);   // raw and rgb_a frames only
+    }
     const codec::Value* tag = has_codec ? d.items[8].get() : nullptr;
     if (tag && tag->items.size() == 1 && tag->items[0]->kind == codec::Value::STR && tag->items[0]->s == planar::kName) {
       // 9th element ('rgb_a',): packed RGB, then the alpha plane.  The whole
@@ -875,11 +902,64 @@ StreamLoader::MappedSegment& StreamLoader::segment(const std::string& name) {
   // RGB only and in place -> it may keep alpha out of the bytes the kernel
   // pulls over the link; anything else needs interleaved pixels
   ms.seg->add_hint(reads_rgb_only() && ms.dev_base ? shm::kWantPlanarAlpha : shm::kNeedInterleaved);
+  // ... and that it keeps slot copies: the producer may report what it rewrote
+  if (mirror_wanted() && ms.dev_base) ms.seg->add_hint(shm::kWantSlotDelta);
+  ms.ring = mirror::Ring(ms.seg->nslots());
   {
     std::lock_guard<std::mutex> lk(mu_);
     seg_list_.push_back(ms.seg.get());   // ring occupancy in stats()
   }
-  return segments_[name] = std::move(ms);
+  MappedSegment& kept = segments_[name] = std::move(ms);
+  by_seg_[kept.seg.get()] = &kept;
+  return kept;
+}
+
+bool StreamLoader::mirror_wanted() const {
+  return cfg_.slot_mirror && cfg_.direct && !cfg_.color_matrix && !cfg_.crop && cfg_.decode_streams == 1;
+}
+
+// The ring's slot mirror for frames of `cin` stored channels (3: rgb_a slots
+// read in place), or null.  It is made when the first frame arrives whose
+// producer reports (`reported`): by then the producer has seen this loader's
+// hints, so the frame has the layout the ring settles on -- the frames
+// published before the hints are read whole, as they would be anyway.  One
+// buffer for all the ring's slots.  None when the budget is spent, the frames
+// are below the configured size or the allocation fails.  A ring that changes
+// its layout later (hints are sticky: a few times in its life at most) gets a
+// new buffer; hipFree waits for the launches that read the old one.
+uint8_t* StreamLoader::slot_mirror(MappedSegment& ms, int cin, bool reported) {
+  if (ms.mirror_dev && ms.mirror_cin == cin) return ms.mirror_dev;
+  if (!reported || ms.mirror_failed) return nullptr;
+  const size_t frame = size_t(H_) * W_ * size_t(cin);
+  const size_t bytes = frame * ms.seg->nslots();
+  if (ms.mirror_dev) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(ms.mirror_dev);
+    const size_t old = size_t(H_) * W_ * size_t(ms.mirror_cin) * ms.seg->nslots();
+    ms.mirror_dev = nullptr;
+    ms.ring = mirror::Ring(ms.seg->nslots());
+    mirror_budget_.release(old);
+    std::lock_guard<std::mutex> lk(mu_);
+    stats_.mirror_bytes -= old;
+  }
+  ms.mirror_cin = cin;
+  ms.mirror_failed = true;
+  if (frame < cfg_.slot_mirror_min_frame_bytes || frame % 16 != 0 || !mirror_budget_.reserve(bytes)) return nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&ms.mirror_dev), bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    ms.mirror_dev = nullptr;
+    mirror_budget_.release(bytes);
+    return nullptr;
+  }
+  ms.mirror_failed = false;
+  std::lock_guard<std::mutex> lk(mu_);
+  stats_.mirror_bytes += bytes;
+  return ms.mirror_dev;
+}
+
+void StreamLoader::invalidate_mirror(shm::Segment* seg, uint32_t slot) {
+  auto it = by_seg_.find(seg);
+  if (it != by_seg_.end()) it->second->ring.invalidate(slot);
 }
 
 void StreamLoader::reap(bool wait_all) {
@@ -913,7 +993,10 @@ void StreamLoader::reap(bool wait_all) {
     }
     uint64_t torn = 0;
     for (auto& s : f.slots) {
-      if (!s.seg->valid(s.slot, s.gen)) torn++;   // a HELD slot taken back (dead-consumer lease)
+      if (!s.seg->valid(s.slot, s.gen)) {   // a HELD slot taken back (dead-consumer lease)
+        torn++;
+        invalidate_mirror(s.seg, s.slot);
+      }
       s.seg->release(s.slot, s.gen);
     }
     if (torn) {
@@ -1287,6 +1370,61 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
         stats_.image_bytes -= whole - window;
       }
     }
+    // Slot mirror (slot_mirror.h): a plain decode of ring frames reads, per
+    // image, only the region its producer reported as rewritten from the host
+    // and the rest from the ring's HBM copy, which the same kernel brings up
+    // to date.  Host order is stream order on the one decode stream, so the
+    // bookkeeping moves to the frame's generation here, when the launch is
+    // queued.  Images without a mirror (pool slots, staged or rebuilt frames,
+    // a ring over the budget) ride in the same launch with a null mirror.
+    //
+    // A launch queued behind one that turns out torn (its slot was taken back
+    // by the producer while the kernel read it) is still correct: the producer
+    // can only have written inside the rectangle of the frame it was drawing,
+    // the next frame of that slot, because the two frames agree everywhere
+    // else.  Torn bytes in the copy therefore lie inside the next frame's own
+    // reported rectangle and are read again from the host by its launch; what
+    // that launch takes from the copy was written by earlier, whole reads.
+    // reap() / promote_ready() invalidate the slot's entry all the same, so
+    // nothing later relies on a copy a torn read produced.
+    const bool mirror_on = plain && !cfg_.crop && mirror_wanted();
+    auto run_plain = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
+      if (!mirror_on) return decode(sp, st);
+      // (RGBA -> RGBA u8 NHWC keeps decode()'s 4-pixel host-read shape, kernels.hip launch_out: not mirrored)
+      const bool raw_rgba = sp.out_dtype == OUT_U8 && sp.layout == NHWC && sp.Cin == 4 && sp.Cout == 4;
+      const bool ok = !raw_rgba && decode_delta_supported(sp);
+      DeltaParams dl;
+      bool any = false;
+      uint64_t saved = 0, deltas = 0;
+      const size_t frame = size_t(H_) * W_ * size_t(sp.Cin);
+      for (size_t n = 0; n < imgs.size(); ++n) {
+        const Item& it = *imgs[n];
+        // the kernel reads this image in its ring slot?  (not a frame staged or rebuilt elsewhere)
+        if (!it.ms || it.staged || !it.expanded.empty()) continue;
+        uint8_t* m = ok ? slot_mirror(*it.ms, sp.Cin, it.has_delta) : nullptr;
+        if (!m) {   // not mirrored (now): whatever the copy held for this slot is no base for a later report
+          it.ms->ring.invalidate(it.slot);
+          continue;
+        }
+        bool used = false;
+        const mirror::Region r = it.ms->ring.decide(it.slot, it.gen, it.has_delta ? &it.delta : nullptr, H_, W_, &used);
+        dl.mirror[n] = m + size_t(it.slot) * frame;
+        dl.y0[n] = int16_t(r.y0), dl.y1[n] = int16_t(r.y1), dl.x0[n] = int16_t(r.x0), dl.x1[n] = int16_t(r.x1);
+        any = true;
+        if (used) {
+          deltas++;
+          saved += uint64_t(int64_t(H_) * W_ - r.pixels()) * uint64_t(sp.Cin);
+        }
+      }
+      if (!any) return decode(sp, st);
+      {
+        // only the regions cross the link: take back what process() counted for whole frames
+        std::lock_guard<std::mutex> lk(mu_);
+        stats_.delta_frames += deltas;
+        stats_.image_bytes -= saved;
+      }
+      return decode_delta(sp, dl, st);
+    };
     if (nplanar > 0 && nplanar < total) {
       // both source layouts in one group (a mixed fleet with inline
       // producers, or the first frames before a producer saw the hint): one
@@ -1297,10 +1435,12 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
         CropParams sc;
         sc.h = crop.h, sc.w = crop.w;
         int n = 0, i = 0;
+        std::vector<const Item*> sub;
         for (auto& b : group)
           for (size_t k = 0; k < b.items.size(); ++k, ++i) {
             const Item& it = *all[size_t(i)];
             if (it.planar != (pl == 1)) continue;
+            sub.push_back(&it);
             sp.srcs[n] = it.dsrc;
             sp.dsts[n] = static_cast<uint8_t*>(b.dst) + k * out_img_bytes;
             if (it.flip) sp.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
@@ -1309,7 +1449,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
           }
         sp.B = sp.nsrcs = sp.ndsts = n;
         sp.Cin = pl == 1 ? 3 : C_;
-        e = cfg_.crop ? decode_crop(sp, sc, st) : decode(sp, st);
+        e = cfg_.crop ? decode_crop(sp, sc, st) : run_plain(sp, sub);
       }
       // (stats_.launches counts launch groups: this one stays one coalesced
       // launch for the batches in it, run as two kernels)
@@ -1326,7 +1466,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       }
       e = decode_tiles(dp, tp, stream_);
     } else {
-      e = cfg_.crop ? decode_crop(dp, crop, st) : decode(dp, st);
+      e = cfg_.crop ? decode_crop(dp, crop, st) : run_plain(dp, all);
     }
   }
   check(e, "decode kernel launch");

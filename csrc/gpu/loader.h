@@ -50,6 +50,7 @@
 #include "../transport/shmring.h"
 #include "../transport/zmtp.h"
 #include "kernels.h"
+#include "slot_mirror.h"
 
 namespace btn {
 namespace gpu {
@@ -143,6 +144,21 @@ struct LoaderConfig {
   // producers for rgb_a frames and leaves the alpha plane in host memory;
   // false = always ask for interleaved frames.
   bool planar_alpha = true;
+  // Slot mirror (slot_mirror.h, kernels.h: decode_delta): keep a byte copy of
+  // every ring slot in HBM and read only the region its producer reports as
+  // rewritten (ring hint kWantSlotDelta) over the link; the rest of the frame
+  // comes from the copy.  Only for direct-path plain decodes on one decode
+  // stream (not the copy path, pass-through, tile16, the colour kernel, crop
+  // or decode_streams > 1), and only for frames the vector kernel takes.  A
+  // slot's first read, and any read whose report does not refer to the
+  // generation the copy holds, is a whole-frame read as without the mirror.
+  // One buffer of nslots x H x W x (3 for rgb_a slots read in place, else C)
+  // bytes per ring, made when its producer first reports and freed with the loader; a ring that
+  // would take the total past slot_mirror_max_bytes gets none, nor do frames
+  // below slot_mirror_min_frame_bytes (0: no lower bound).
+  bool slot_mirror = true;
+  size_t slot_mirror_max_bytes = size_t(1) << 30;
+  size_t slot_mirror_min_frame_bytes = 0;
   // decode parameters (src/dst/B/H/W/Cin filled per batch)
   int cout = 3;
   int cmap[4] = {0, 1, 2, 3};
@@ -230,6 +246,8 @@ struct LoaderStats {
   uint64_t image_bytes = 0;                // image bytes that crossed host -> device
   uint64_t tiled_frames = 0;               // key-frame delta frames (tiledelta.h)
   uint64_t planar_frames = 0;              // shm frames that arrived as rgb_a (planar_alpha.h)
+  uint64_t delta_frames = 0;               // frames of which only the reported region was read from the host
+  uint64_t mirror_bytes = 0;               // HBM held by slot mirrors
   double h2d_issue_ms = 0;
   // GPU time of every kTimedEvery-th launch (timing events around its H2D
   // copies + decode kernel): per-image device cost without timing every launch
@@ -271,12 +289,16 @@ class StreamLoader {
 
  private:
   struct KeyFrame;
+  struct MappedSegment;
   struct Item {
     zmtp::Frame frame;
     const uint8_t* src = nullptr;      // image bytes: in the frame or in a shm slot
     const uint8_t* dsrc = nullptr;     // device-visible alias of `src` (pinned + mapped), or null
     shm::Segment* seg = nullptr;       // shared-memory slot to hand back, if any
     uint32_t slot = 0, gen = 0;
+    MappedSegment* ms = nullptr;       // the ring `seg` belongs to (slot mirror)
+    bool has_delta = false;            // descriptor element 10 (shmring.h: kWantSlotDelta)
+    mirror::Delta delta;
     bool flip = false;
     // key-frame delta (csrc/codec/tiledelta.h): `src`/`dsrc` point at the
     // encoded frame (ntiles payload tiles); the key frame is at key_host (shm)
@@ -391,7 +413,18 @@ class StreamLoader {
   struct MappedSegment {
     std::unique_ptr<shm::Segment> seg;
     uint8_t* dev_base = nullptr;   // device-visible alias of seg->base()
+    // slot mirror: nslots x H x W x mirror_cin bytes in HBM (null: none) and
+    // the generation it holds per slot
+    uint8_t* mirror_dev = nullptr;
+    int mirror_cin = 0;
+    bool mirror_failed = false;    // no buffer for this ring (budget, frame size, allocation): not tried again
+    mirror::Ring ring;
   };
+  bool mirror_wanted() const;                           // this loader's configuration can use slot mirrors
+  uint8_t* slot_mirror(MappedSegment& ms, int cin, bool reported);   // the ring's mirror for such frames, or null
+  void invalidate_mirror(shm::Segment* seg, uint32_t slot);
+  std::map<const shm::Segment*, MappedSegment*> by_seg_;
+  mirror::Budget mirror_budget_;
   MappedSegment& segment(const std::string& name);
   std::map<std::string, MappedSegment> segments_;   // mapped + hipHostRegister'ed
   struct KeyFrame {

@@ -286,6 +286,43 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0, py::arg("unroll") = 0,
         py::arg("crop_size") = std::vector<int>(), py::arg("crop") = std::vector<int>());
 
+  // Region read + slot mirror (kernels.h: decode_delta) at the pointer level: srcs[b] the frame (usually
+  // host memory), mirrors[b] its device copy (0: none, the whole image comes from srcs[b]), regions =
+  // B x (y0, y1, x0, x1) in stored rows / pixel columns, inclusive (y1 < y0: nothing from srcs[b]).
+  m.def("decode_delta",
+        [](std::vector<uintptr_t> srcs, std::vector<uintptr_t> mirrors, std::vector<int> regions, uintptr_t dst,
+           uintptr_t lut, int B, int H, int W, int Cin, int Cout, std::vector<int> cmap, int flip_all, int out_dtype,
+           int layout, uintptr_t stream, std::vector<uintptr_t> dsts, std::vector<uint64_t> flip_bits, int max_grid) {
+          if (B < 0 || B > kMaxSrcs || srcs.size() > size_t(kMaxSrcs) || dsts.size() > size_t(kMaxSrcs))
+            throw std::invalid_argument("decode_delta: at most kMaxSrcs (64) images");
+          if (mirrors.size() != size_t(B) || regions.size() != size_t(B) * 4)
+            throw std::invalid_argument("decode_delta: mirrors holds B pointers and regions (y0, y1, x0, x1) per image");
+          DecodeParams p;
+          fill_image_lists(p, srcs, dsts, flip_bits, "decode_delta");
+          DeltaParams d;
+          for (int b = 0; b < B; ++b) {
+            d.mirror[b] = ptr<uint8_t>(mirrors[size_t(b)]);
+            for (int k = 0; k < 4; ++k)
+              if (regions[size_t(b) * 4 + k] < INT16_MIN || regions[size_t(b) * 4 + k] > INT16_MAX)
+                throw std::invalid_argument("decode_delta: region out of range");
+            d.y0[b] = int16_t(regions[size_t(b) * 4]), d.y1[b] = int16_t(regions[size_t(b) * 4 + 1]);
+            d.x0[b] = int16_t(regions[size_t(b) * 4 + 2]), d.x1[b] = int16_t(regions[size_t(b) * 4 + 3]);
+          }
+          p.max_grid = max_grid;
+          p.dst = ptr<void>(dst);
+          p.lut = ptr<const float>(lut);
+          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+          fill_cmap(p.cmap, cmap);
+          p.flip_all = flip_all;
+          p.out_dtype = out_dtype;
+          p.layout = layout;
+          check(decode_delta(p, d, stream_of(stream)), "decode_delta");
+        },
+        py::arg("srcs"), py::arg("mirrors"), py::arg("regions"), py::arg("dst"), py::arg("lut"), py::arg("B"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"),
+        py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("dsts") = std::vector<uintptr_t>(),
+        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0);
+
   // Key-frame delta decode (kernels.h: decode_tiles) at the pointer level: srcs[b] the encoded frame,
   // fills[b] image b's decoded key frame, tile_start the prefix sums of the payload tile counts.
   m.def("decode_tiles",
@@ -1250,8 +1287,12 @@ PYBIND11_MODULE(_hip, m) {
                        std::vector<float> bias, bool direct, int launch_depth, int copy_streams, bool host_sync,
                        std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed,
                        bool planar_alpha, int decode_streams, std::vector<int> crop, const std::string& crop_mode,
-                       std::vector<int> crop_origin, double mirror, int x_align, uint64_t crop_seed) {
+                       std::vector<int> crop_origin, double mirror, int x_align, uint64_t crop_seed,
+                       bool slot_mirror, size_t slot_mirror_max_bytes, size_t slot_mirror_min_frame_bytes) {
              LoaderConfig c;
+             c.slot_mirror = slot_mirror;
+             c.slot_mirror_max_bytes = slot_mirror_max_bytes;
+             c.slot_mirror_min_frame_bytes = slot_mirror_min_frame_bytes;
              c.direct = direct;
              c.decode_streams = decode_streams;
              c.planar_alpha = planar_alpha;
@@ -1317,7 +1358,8 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("jitter") = std::vector<float>(), py::arg("jitter_seed") = 0, py::arg("planar_alpha") = true,
            py::arg("decode_streams") = 1, py::arg("crop") = std::vector<int>(), py::arg("crop_mode") = "random",
            py::arg("crop_origin") = std::vector<int>(), py::arg("mirror") = 0.0, py::arg("x_align") = 1,
-           py::arg("crop_seed") = 0)
+           py::arg("crop_seed") = 0, py::arg("slot_mirror") = true,
+           py::arg("slot_mirror_max_bytes") = size_t(1) << 30, py::arg("slot_mirror_min_frame_bytes") = 0)
       .def("start", &StreamLoader::start)
       .def("wait_shape",
            [](StreamLoader& l, long timeout_ms) -> py::object {
@@ -1398,6 +1440,8 @@ PYBIND11_MODULE(_hip, m) {
         d["image_bytes"] = s.image_bytes;
         d["tiled_frames"] = s.tiled_frames;
         d["planar_frames"] = s.planar_frames;
+        d["delta_frames"] = s.delta_frames;
+        d["mirror_bytes"] = s.mirror_bytes;
         d["timed_launches"] = s.timed_launches;
         d["timed_images"] = s.timed_images;
         d["timed_gpu_ms"] = s.timed_gpu_ms;

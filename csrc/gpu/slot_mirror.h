@@ -1,0 +1,114 @@
+// Slot mirror bookkeeping (host only, no HIP calls).
+//
+// The loader reads every ring slot again and again, and the producer rewrites
+// only part of a slot between two uses.  With a byte copy of every slot in
+// HBM (the "slot mirror") a decode needs only the rewritten part from the
+// host.  The producer reports that part in descriptor element 10
+// (shmring.h: kWantSlotDelta): (base_gen, y0, y1, x0, x1) -- every byte
+// outside stored rows [y0, y1] x pixel columns [x0, x1] equals what the slot
+// held when it was published with generation base_gen.
+//
+// This header keeps, per mapped ring, which generation the mirror holds for
+// every slot, and decides per frame which region the kernel has to read from
+// the host (kernels.h: decode_delta).  It never looks at pixels.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace btn {
+namespace gpu {
+namespace mirror {
+
+// Region of a frame in stored rows x pixel columns, inclusive.  Empty: y1 < y0.
+struct Region {
+  int y0 = 0, y1 = -1, x0 = 0, x1 = -1;
+  bool empty() const { return y1 < y0 || x1 < x0; }
+  int64_t pixels() const { return empty() ? 0 : int64_t(y1 - y0 + 1) * (x1 - x0 + 1); }
+  bool whole(int H, int W) const { return y0 == 0 && x0 == 0 && y1 == H - 1 && x1 == W - 1; }
+};
+
+// Descriptor element 10.
+struct Delta {
+  uint32_t base_gen = 0;
+  Region rect;
+};
+
+// A reported rectangle is either empty (y1 < y0: nothing changed) or lies in the frame.
+inline bool delta_valid(const Delta& d, int H, int W) {
+  const Region& r = d.rect;
+  if (r.y1 < r.y0) return true;
+  return r.y0 >= 0 && r.y1 < H && r.x0 >= 0 && r.x0 <= r.x1 && r.x1 < W;
+}
+
+// The kernel takes a lane's whole pixel group from one side, so a region
+// starts and ends on multiples of kAlign pixels (or at the frame's edge):
+// every run of region bytes then starts and ends on a 64-byte line for 3-
+// and 4-byte pixels alike.
+constexpr int kAlign = 64;
+
+inline Region widen(const Region& r, int W) {
+  if (r.empty()) return Region();
+  Region o = r;
+  if (W % kAlign != 0) {   // rows do not start on a block boundary: full rows
+    o.x0 = 0, o.x1 = W - 1;
+    return o;
+  }
+  o.x0 = r.x0 / kAlign * kAlign;
+  o.x1 = (r.x1 / kAlign + 1) * kAlign - 1;
+  if (o.x1 > W - 1) o.x1 = W - 1;
+  return o;
+}
+
+// HBM the mirrors of one loader may take.
+class Budget {
+ public:
+  explicit Budget(size_t max_bytes = 0) : max_(max_bytes) {}
+  bool reserve(size_t bytes) {
+    if (bytes > max_ || used_ > max_ - bytes) return false;
+    used_ += bytes;
+    return true;
+  }
+  void release(size_t bytes) { used_ -= bytes <= used_ ? bytes : used_; }
+  size_t used() const { return used_; }
+
+ private:
+  size_t max_, used_ = 0;
+};
+
+// One ring: the generation the mirror holds per slot.
+class Ring {
+ public:
+  explicit Ring(uint32_t nslots = 0) : gen_(nslots, 0), held_(nslots, 0) {}
+  uint32_t nslots() const { return uint32_t(gen_.size()); }
+  bool holds(uint32_t slot, uint32_t gen) const { return slot < gen_.size() && held_[slot] && gen_[slot] == gen; }
+  void invalidate(uint32_t slot) {
+    if (slot < held_.size()) held_[slot] = 0;
+  }
+  // The region of generation `gen` of `slot` to read from the host: the
+  // reported rectangle, widened, when the mirror holds the generation the
+  // report is relative to; else the whole frame.  Afterwards the mirror
+  // holds `gen` (the caller queues the kernel that makes it so).
+  // *from_delta: the report was used.
+  Region decide(uint32_t slot, uint32_t gen, const Delta* d, int H, int W, bool* from_delta = nullptr) {
+    Region r;
+    const bool use = d && slot < gen_.size() && holds(slot, d->base_gen) && delta_valid(*d, H, W);
+    if (use) {
+      r = widen(d->rect, W);
+    } else {
+      r.y0 = 0, r.y1 = H - 1, r.x0 = 0, r.x1 = W - 1;
+    }
+    if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
+    if (from_delta) *from_delta = use;
+    return r;
+  }
+
+ private:
+  std::vector<uint32_t> gen_;
+  std::vector<uint8_t> held_;
+};
+
+}  // namespace mirror
+}  // namespace gpu
+}  // namespace btn

@@ -222,8 +222,14 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
   std::vector<std::vector<uint8_t>> slots(kSlots, std::vector<uint8_t>(n));
   std::vector<sim::DirtyRect> dirty(kSlots);
   std::vector<std::vector<uint8_t>> fulls(kSlots, std::vector<uint8_t>(n));   // as cold as the slots
+  // a byte mirror per slot, updated only inside the rectangle a consumer
+  // would be told about (changed_rect: descriptor element 10): it must stay
+  // equal to the slot
+  std::vector<std::vector<uint8_t>> mirrors(kSlots, std::vector<uint8_t>(n));
+  const int mc = planar ? 3 : r.channels();      // channels of the bytes a rectangle covers (rgb_a: the RGB part)
+  const bool lower_left = a.origin == "lower-left";
   double t_full = 0, t_inc = 0;
-  long long mismatches = 0;
+  long long mismatches = 0, mirror_mismatches = 0;
   uint64_t h = 1469598103934665603ull;   // FNV-1a over every incremental frame
   int frame = a.frame_start;
   for (long long i = 0; i < a.bench; ++i) {
@@ -234,6 +240,12 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
     r.render(scene, fulls[size_t(i % kSlots)].data());
     auto t1 = std::chrono::steady_clock::now();
     uint8_t* out = slots[size_t(i % kSlots)].data();
+    sim::DirtyRect before;
+    const bool was_known = dirty[size_t(i % kSlots)].known;
+    {
+      const sim::DirtyRect& d = dirty[size_t(i % kSlots)];
+      before.x0 = d.x0, before.y0 = d.y0, before.x1 = d.x1, before.y1 = d.y1;
+    }
     if (planar) {
       if (!dirty[size_t(i % kSlots)].known) fill_alpha_plane(out, npix);
       planar->render(scene, out, &dirty[size_t(i % kSlots)]);
@@ -243,6 +255,19 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
     auto t2 = std::chrono::steady_clock::now();
     t_full += std::chrono::duration<double, std::milli>(t1 - t0).count();
     t_inc += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    {
+      uint8_t* mir = mirrors[size_t(i % kSlots)].data();
+      if (!was_known) {
+        std::memcpy(mir, out, n);   // a slot's first frame is taken whole
+      } else {
+        const sim::StoredRect c = sim::changed_rect(before, dirty[size_t(i % kSlots)], r.height(), lower_left);
+        for (int y = c.y0; !c.empty() && y <= c.y1; ++y) {
+          const size_t o = (size_t(y) * r.width() + size_t(c.x0)) * size_t(mc);
+          std::memcpy(mir + o, out + o, size_t(c.x1 - c.x0 + 1) * size_t(mc));
+        }
+      }
+      for (size_t k = 0; k < n; ++k) mirror_mismatches += mir[k] != out[k];
+    }
     // compared (and hashed) in the frame's logical HWC byte order; a planar
     // slot is read where it lies, so both layouts touch the same memory here
     for (size_t k = 0; k < n; ++k) {
@@ -252,9 +277,9 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
     }
   }
   std::printf("{\"frames\": %lld, \"full_ms\": %.4f, \"incremental_ms\": %.4f, \"mismatched_bytes\": %lld, "
-              "\"checksum\": \"%016llx\"}\n",
-              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, (unsigned long long)h);
-  return mismatches == 0 ? 0 : 1;
+              "\"mirror_mismatched_bytes\": %lld, \"checksum\": \"%016llx\"}\n",
+              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, mirror_mismatches, (unsigned long long)h);
+  return mismatches == 0 && mirror_mismatches == 0 ? 0 : 1;
 }
 
 }  // namespace
@@ -353,6 +378,10 @@ int main(int argc, char** argv) {
   // unknown content (full background copy; alpha plane filled for rgb_a)
   enum SlotLayout : uint8_t { kUnknown = 0, kInterleaved = 1, kPlanar = 2 };
   std::vector<uint8_t> slot_layout(seg ? size_t(a.shm_slots) : 0, uint8_t(kUnknown));
+  // kWantSlotDelta (shmring.h): the generation each slot was last published
+  // with by THIS producer (0: never, or not to be relied on) -- kept here, not
+  // read back from the slot word, which a lease reclaim bumps
+  std::vector<uint32_t> slot_gen(seg ? size_t(a.shm_slots) : 0, 0u);
   const size_t npix = size_t(W) * H;
   const auto t_start = std::chrono::steady_clock::now();
   auto next_due = t_start;
@@ -403,6 +432,67 @@ int main(int argc, char** argv) {
       w.key("origin");
       w.str("lower-left");
     }
+    // Render into `pixels`.  A ring frame is drawn BEFORE its descriptor is
+    // written (the descriptor reports what the render changed), an inline
+    // frame after: its pixels live in the message itself.
+    sim::DirtyRect before;       // ring slot of known content: the rectangle its last frame left
+    bool delta_known = false;    // ... and this producer knows the generation that content was published with
+    sim::StoredRect changed;
+    auto draw = [&](uint8_t* pixels) {
+      sim::DirtyRect* dirty = tiled ? &tiled_dirty : (seg && incremental ? &slot_dirty[size_t(slot)] : nullptr);
+      uint8_t* const slot_bytes = pixels;
+      if (tiled) pixels = tiled_frame.data();
+      if (seg && !tiled) {
+        uint8_t& held = slot_layout[size_t(slot)];
+        const uint8_t now = planar ? kPlanar : kInterleaved;
+        if (held != now) {
+          slot_dirty[size_t(slot)] = sim::DirtyRect();   // unknown content: full background copy
+          if (planar) fill_alpha_plane(pixels, npix);
+          held = now;
+        }
+        // what the slot's known content is about to lose (render() restores
+        // it) -- together with what this frame leaves, all that changes
+        if (dirty && dirty->known) {
+          before.x0 = dirty->x0, before.y0 = dirty->y0, before.x1 = dirty->x1, before.y1 = dirty->y1;
+          delta_known = slot_gen[size_t(slot)] != 0;
+        }
+      }
+      (planar ? planar_renderer() : renderer()).render(scene, pixels, dirty);
+      if (a.stamp) {
+        // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
+        // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
+        uint8_t st[16] = {'B', 'T', uint8_t(a.btid & 0xff), uint8_t((a.btid >> 8) & 0xff), 0, 0, 0, 0};
+        const uint64_t q = uint64_t(published);
+        std::memcpy(st + 8, &q, 8);
+        if (planar) {
+          // the same 16 logical HWC bytes: pixels 0..3, their alpha (bytes 3, 7,
+          // 11, 15) in the alpha plane -- rewritten every frame, never restored
+          for (int p = 0; p < 4; ++p) {
+            std::memcpy(pixels + 3 * p, st + 4 * p, 3);
+            pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
+            const int row = p / W, col = p % W;   // stored row / column of pixel p
+            if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
+          }
+        } else {
+          std::memcpy(pixels, st, sizeof(st));
+          if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+        }
+      }
+      if (tiled) {
+        // everything outside this frame's dirty rectangle is background
+        if (tiled_dirty.empty())
+          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, 0, -1, 0, -1, slot_bytes);
+        else if (lower_left)   // DirtyRect rows are image rows (0 = top); stored rows are flipped
+          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, H - 1 - tiled_dirty.y1, H - 1 - tiled_dirty.y0,
+                            tiled_dirty.x0, tiled_dirty.x1, slot_bytes);
+        else
+          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, tiled_dirty.y0, tiled_dirty.y1, tiled_dirty.x0,
+                            tiled_dirty.x1, slot_bytes);
+      }
+      if (delta_known) changed = sim::changed_rect(before, *dirty, H, lower_left);
+    };
+    auto r0 = std::chrono::steady_clock::now();
+    if (seg) draw(seg->slot(uint32_t(slot)));
     if (seg) {
       // descriptor: (segment, slot, byte offset, H, W, C, image key, generation)
       gen = ((seg->state(uint32_t(slot)) >> 2) + 1) & 0x3fffffffu;   // publish() will bump to this
@@ -427,58 +517,30 @@ int main(int argc, char** argv) {
         w.str(planar::kName);
         w.end_tuple();
       }
+      // 10th element (base_gen, y0, y1, x0, x1) for a consumer that keeps slot
+      // copies (shmring.h: kWantSlotDelta); never for tile16 frames, a full
+      // render or a slot whose content or layout is not the one last published
+      if (!tiled && delta_known && (seg->hint() & shm::kWantSlotDelta)) {
+        if (!planar) w.none();   // interleaved frames have no 9th element: a non-tuple means "no codec"
+        w.begin_tuple();
+        w.integer(slot_gen[size_t(slot)]);
+        w.integer(changed.empty() ? 0 : changed.y0);
+        w.integer(changed.empty() ? -1 : changed.y1);
+        w.integer(changed.empty() ? 0 : changed.x0);
+        w.integer(changed.empty() ? -1 : changed.x1);
+        w.end_tuple();
+      }
       w.end_tuple();
     }
     w.end_dict();
     auto& buf = w.finish();
     uint8_t* pixels = seg ? seg->slot(uint32_t(slot)) : buf.data() + img_off;
 
-    auto r0 = std::chrono::steady_clock::now();
-    sim::DirtyRect* dirty = tiled ? &tiled_dirty : (seg && incremental ? &slot_dirty[size_t(slot)] : nullptr);
-    uint8_t* const slot_bytes = pixels;
-    if (tiled) pixels = tiled_frame.data();
-    if (seg && !tiled) {
-      uint8_t& held = slot_layout[size_t(slot)];
-      const uint8_t now = planar ? kPlanar : kInterleaved;
-      if (held != now) {
-        slot_dirty[size_t(slot)] = sim::DirtyRect();   // unknown content: full background copy
-        if (planar) fill_alpha_plane(pixels, npix);
-        held = now;
-      }
+    if (!seg) draw(pixels);
+    if (seg) {
+      seg->publish(uint32_t(slot));   // == gen
+      slot_gen[size_t(slot)] = gen;
     }
-    (planar ? planar_renderer() : renderer()).render(scene, pixels, dirty);
-    if (a.stamp) {
-      // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
-      // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
-      uint8_t st[16] = {'B', 'T', uint8_t(a.btid & 0xff), uint8_t((a.btid >> 8) & 0xff), 0, 0, 0, 0};
-      const uint64_t q = uint64_t(published);
-      std::memcpy(st + 8, &q, 8);
-      if (planar) {
-        // the same 16 logical HWC bytes: pixels 0..3, their alpha (bytes 3, 7,
-        // 11, 15) in the alpha plane -- rewritten every frame, never restored
-        for (int p = 0; p < 4; ++p) {
-          std::memcpy(pixels + 3 * p, st + 4 * p, 3);
-          pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
-          const int row = p / W, col = p % W;   // stored row / column of pixel p
-          if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
-        }
-      } else {
-        std::memcpy(pixels, st, sizeof(st));
-        if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
-      }
-    }
-    if (tiled) {
-      // everything outside this frame's dirty rectangle is background
-      if (tiled_dirty.empty())
-        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, 0, -1, 0, -1, slot_bytes);
-      else if (lower_left)   // DirtyRect rows are image rows (0 = top); stored rows are flipped
-        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, H - 1 - tiled_dirty.y1, H - 1 - tiled_dirty.y0,
-                          tiled_dirty.x0, tiled_dirty.x1, slot_bytes);
-      else
-        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, tiled_dirty.y0, tiled_dirty.y1, tiled_dirty.x0,
-                          tiled_dirty.x1, slot_bytes);
-    }
-    if (seg) seg->publish(uint32_t(slot));   // == gen
     render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
 
     if (a.fault != "none" && a.fault_after >= 0 && published == a.fault_after) {
@@ -495,7 +557,10 @@ int main(int argc, char** argv) {
         } catch (const zmtp::Error&) {
           break;
         }
-        if (seg) seg->release(uint32_t(slot), seg->publish(uint32_t(slot)));
+        if (seg) {
+          seg->release(uint32_t(slot), seg->publish(uint32_t(slot)));
+          slot_gen[size_t(slot)] = 0;   // published twice: no consumer saw a generation to refer to
+        }
         ++published;
         continue;
       }

@@ -103,6 +103,26 @@ struct DirtyRect {
   }
 };
 
+// What a render into a buffer of known content changed, in STORED rows (a
+// lower-left frame stores image row y at H - 1 - y): the union of the
+// rectangle the render restored (`before`) and the one it left (`after`).
+// Every byte outside it is what the buffer held before.  Empty: y1 < y0.
+struct StoredRect {
+  int y0 = 0, y1 = -1, x0 = 0, x1 = -1;
+  bool empty() const { return y1 < y0 || x1 < x0; }
+};
+inline StoredRect changed_rect(const DirtyRect& before, const DirtyRect& after, int H, bool lower_left) {
+  DirtyRect u;
+  if (!before.empty()) u.add(before.y0, before.x0, before.x1), u.add(before.y1, before.x0, before.x1);
+  if (!after.empty()) u.add(after.y0, after.x0, after.x1), u.add(after.y1, after.x0, after.x1);
+  StoredRect r;
+  if (u.empty()) return r;
+  r.x0 = u.x0, r.x1 = u.x1;
+  r.y0 = lower_left ? H - 1 - u.y1 : u.y0;
+  r.y1 = lower_left ? H - 1 - u.y0 : u.y1;
+  return r;
+}
+
 // Frame renderer.  Camera, light and ground plane are static for the life of
 // a Renderer, so their shading (the whole background) is computed once and
 // cached together with each pixel's ground-plane hit point; a frame then costs

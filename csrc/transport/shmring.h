@@ -21,7 +21,13 @@
 // kWantPlanarAlpha alone stores them as `rgb_a` (csrc/common/planar_alpha.h:
 // H*W*3 bytes of packed RGB, then the H*W alpha plane; descriptor element 9 =
 // ('rgb_a',)), and such a consumer reads only the first three quarters of
-// the slot.
+// the slot.  kWantSlotDelta: a consumer keeps a byte copy of every slot and
+// asks the producer to say which part of a slot it rewrote: descriptor
+// element 10 = (base_gen, y0, y1, x0, x1) -- every byte of the frame outside
+// stored rows [y0, y1] x pixel columns [x0, x1] (inclusive; y1 < y0: nothing
+// changed) equals what this slot held when it was published with generation
+// base_gen.  A producer that does not know (the Python publisher, a slot of
+// unknown content, tile16) leaves the element out.
 // Slot word = generation << 2 | state.  States: FREE (0) -> WRITING (1,
 // producer) -> PUBLISHED (2, generation bumped) -> HELD (3, a consumer took
 // the descriptor: CAS on the exact published word) -> FREE (consumer, after
@@ -53,6 +59,7 @@ constexpr uint32_t kVersion = 2;
 // consumer hint bits (Header::hint)
 constexpr uint32_t kWantPlanarAlpha = 1;
 constexpr uint32_t kNeedInterleaved = 2;
+constexpr uint32_t kWantSlotDelta = 4;
 
 struct Header {
   uint64_t magic;

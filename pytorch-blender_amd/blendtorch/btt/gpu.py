@@ -41,6 +41,7 @@ logger = logging.getLogger('blendtorch')
 __all__ = ['DeviceLoader', 'DecodeConfig']
 
 DEFAULT_DECODE_STREAMS = 1   # csrc/gpu/loader.h LoaderConfig::decode_streams
+SLOT_MIRROR_AUTO_MIN_BYTES = 64 * 1024   # DeviceLoader(slot_mirror=None): smallest frame that gets a slot mirror
 
 
 def _default_io_threads(addresses) -> int:
@@ -100,6 +101,21 @@ class DeviceLoader:
         followed by the alpha plane -- and its kernel reads only the first
         three quarters of each RGBA slot over PCIe (``planar_frames`` in
         :attr:`stats`).  ``'interleaved'``: always ask for interleaved frames.
+    slot_mirror: bool, optional
+        Keep a byte copy of every producer ring slot in HBM and read over PCIe
+        only the part of a slot its producer reports as rewritten since the
+        copy was made (ring hint ``kWantSlotDelta``, csrc/gpu/slot_mirror.h);
+        the rest of the frame comes from the copy.  A slot's first read is a
+        whole-frame read, as is every frame of a producer that reports
+        nothing (the Python publisher).  Direct-path plain decodes on one
+        decode stream only.  ``None`` (default): on for frames of at least
+        ``SLOT_MIRROR_AUTO_MIN_BYTES`` read bytes -- below that a launch is
+        bound by its latency, not by the link, and the copies would only cost
+        HBM; ``True``: on for every frame size; ``False``: off.
+        ``delta_frames`` and ``mirror_bytes`` in :attr:`stats` count the
+        frames read by region and the HBM the copies take;
+        ``slot_mirror_max_bytes`` (default 1 GiB) bounds the latter: a ring
+        that would exceed it is read whole, as without the mirror.
     launch_depth: int
         Direct-path decode launches the loader keeps queued on its stream.
         Batches completing while that many are in flight wait and go out
@@ -148,7 +164,8 @@ class DeviceLoader:
                  skip_bad: bool = False, meta_to_device: bool = False, staging_depth: int = 3, h2d: str = 'auto',
                  launch_depth: int = 2, log_every: Optional[float] = None, copy_streams: int = 2,
                  defer_post: bool = False, host_sync: Optional[bool] = None, reuse_buffers: bool = False,
-                 shm_alpha: str = 'auto', decode_streams: Optional[int] = None):
+                 shm_alpha: str = 'auto', decode_streams: Optional[int] = None,
+                 slot_mirror: Optional[bool] = None, slot_mirror_max_bytes: int = 1 << 30):
         if h2d not in ('auto', 'copy'):
             raise ValueError("h2d must be 'auto' or 'copy'")
         # None: the native default (1), or the BT_LOADER_DECODE_STREAMS diagnostic
@@ -161,6 +178,8 @@ class DeviceLoader:
         if shm_alpha not in ('auto', 'interleaved'):
             raise ValueError("shm_alpha must be 'auto' or 'interleaved'")
         self.h2d = h2d
+        self.slot_mirror = None if slot_mirror is None else bool(slot_mirror)
+        self.slot_mirror_max_bytes = int(slot_mirror_max_bytes)
         self.shm_alpha = shm_alpha
         self.launch_depth = int(launch_depth)
         self.copy_streams = max(1, min(4, int(copy_streams)))
@@ -264,7 +283,9 @@ class DeviceLoader:
             max_batches, 0, 0, self.staging_depth, self.skip_bad, cfg.cout, list(cfg.cmap) + [0] * (4 - len(cfg.cmap)),
             int(cfg.flip), ops.OUT_DTYPES[cfg.dtype], ops.LAYOUTS[cfg.layout], lut, matrix, bias,
             self.h2d == 'auto', self.launch_depth, self.copy_streams, self.host_sync, matrices, jitter, seed,
-            self.shm_alpha == 'auto', self.decode_streams, **crop)
+            self.shm_alpha == 'auto', self.decode_streams, slot_mirror=self.slot_mirror is not False,
+            slot_mirror_max_bytes=self.slot_mirror_max_bytes,
+            slot_mirror_min_frame_bytes=SLOT_MIRROR_AUTO_MIN_BYTES if self.slot_mirror is None else 0, **crop)
 
     def _post(self, loader, stream):
         shape = self.decode.out_shape(self.batch_size, *self.shape[:2])
@@ -333,6 +354,7 @@ class DeviceLoader:
             'direct_batches': s['direct_batches'],
             'staged_frames': s.get('staged_frames', 0),
             'planar_frames': s.get('planar_frames', 0),
+            'delta_frames': s.get('delta_frames', 0),
             'consumer_wait_s': self._wait_s,
             'bad': s['bad'], 'shm_stale': s['shm_stale'], 'shm_torn': s['shm_torn'],
             'pool_fallbacks': s['pool_fallbacks'],

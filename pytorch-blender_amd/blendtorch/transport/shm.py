@@ -7,7 +7,11 @@ element ``('tile16', key_segment, key_generation)`` marks a key-frame delta
 frame (csrc/codec/tiledelta.h), which :func:`resolve` rebuilds; a 9th element
 ``('rgb_a',)`` marks an RGBA frame stored as H*W*3 bytes of packed RGB followed
 by its H*W alpha bytes (csrc/common/planar_alpha.h), which :func:`resolve`
-re-interleaves into the same ``H x W x 4`` array.  The GPU loader DMAs the
+re-interleaves into the same ``H x W x 4`` array.  A 10th element ``(base_gen,
+y0, y1, x0, x1)`` (9th then ``None`` for raw frames) is sent while a consumer set
+``WANT_SLOT_DELTA``: all bytes outside stored rows [y0, y1] x columns [x0, x1]
+equal the slot's content at generation ``base_gen``; :func:`resolve` ignores it.
+The GPU loader DMAs the
 slot in place; CPU consumers call :func:`resolve`, which copies the image into
 the dict under ``key`` and hands the slot back.  :class:`ShmRing` is the
 producer side for Python publishers (``btb.DataPublisher(shm_slots=N)``).
@@ -41,6 +45,7 @@ VERSION = 2
 _HDR = struct.Struct('<QIIQQII')
 _HINT_WORD = 8            # index of the hint among the header's u32 words
 WANT_PLANAR_ALPHA, NEED_INTERLEAVED = 1, 2    # csrc/transport/shmring.h hint bits
+WANT_SLOT_DELTA = 4
 FREE, WRITING, PUBLISHED, HELD = 0, 1, 2, 3
 HELD_LEASE_FACTOR = 20    # csrc/transport/shmring.h kHeldLeaseFactor
 KEY = '_btshm'
