@@ -454,6 +454,235 @@ VPtr parse(const uint8_t* data, size_t n) {
   return root;
 }
 
+// --------------------------------------------------------------------------
+// Descriptor scan: the pickle machine over a fixed stack of light values.
+// Only what the result needs is kept (integers, string spans, tuples of
+// those); every other value is an opaque OTHER that is pushed and popped with
+// the right stack effect.  The top-level dict's pairs are read where the
+// stream sets them (SETITEM / SETITEMS on stack slot 0).
+// --------------------------------------------------------------------------
+namespace {
+
+struct Light {   // (no initialisers: the scanner's arrays stay unwritten until used)
+  enum Kind : uint8_t { OTHER, INT, STR, TUPLE, ROOT } kind;
+  uint16_t kid0, nkids;   // TUPLE: its elements in the arena
+  int64_t i;
+  Span s;
+  Light() {}
+  explicit Light(Kind k) : kind(k), kid0(0), nkids(0), i(0) {}
+};
+
+class DescriptorScanner {
+ public:
+  DescriptorScanner(const uint8_t* d, size_t n, const char* image_key, DescriptorScan* out)
+      : d_(d), n_(n), image_key_(image_key), out_(out) {}
+
+  bool run() {
+    while (p_ < n_) {
+      const uint8_t op = d_[p_++];
+      switch (op) {
+        case PROTO: if (!need(1)) return false; p_ += 1; break;
+        case FRAME: if (!need(8)) return false; p_ += 8; break;
+        case STOP: return h_ == 1 && nmarks_ == 0 && st_[0].kind == Light::ROOT && seen_shm_;
+        case MARK: if (nmarks_ == kMarks) return false; marks_[nmarks_++] = h_; break;
+        case NONE_: case NEWTRUE: case NEWFALSE: case EMPTY_LIST: case EMPTY_SET:
+          if (!push(Light(Light::OTHER))) return false;
+          break;
+        case EMPTY_DICT: {
+          Light v(Light::OTHER);
+          if (h_ == 0 && !root_made_) v.kind = Light::ROOT, root_made_ = true;
+          if (!push(v)) return false;
+          break;
+        }
+        case EMPTY_TUPLE: if (!make_tuple(0)) return false; break;
+        case BININT: { if (!need(4)) return false; int32_t x; std::memcpy(&x, d_ + p_, 4); p_ += 4; if (!push_int(x)) return false; break; }
+        case BININT1: { if (!need(1)) return false; if (!push_int(d_[p_++])) return false; break; }
+        case BININT2: { if (!need(2)) return false; uint16_t x; std::memcpy(&x, d_ + p_, 2); p_ += 2; if (!push_int(x)) return false; break; }
+        case LONG1: {
+          if (!need(1)) return false;
+          const size_t k = d_[p_++];
+          if (k > 8 || !need(k)) return false;
+          int64_t x = 0;
+          for (size_t i = 0; i < k; ++i) x |= int64_t(d_[p_ + i]) << (8 * i);
+          if (k > 0 && k < 8 && (d_[p_ + k - 1] & 0x80)) x -= int64_t(1) << (8 * k);
+          p_ += k;
+          if (!push_int(x)) return false;
+          break;
+        }
+        case BINFLOAT: if (!need(8)) return false; p_ += 8; if (!push(Light(Light::OTHER))) return false; break;
+        case SHORT_BINUNICODE: { if (!need(1)) return false; if (!push_str(d_[p_++])) return false; break; }
+        case BINUNICODE: { if (!need(4)) return false; uint32_t k; std::memcpy(&k, d_ + p_, 4); p_ += 4; if (!push_str(k)) return false; break; }
+        case SHORT_BINBYTES: { if (!need(1)) return false; if (!skip_bytes(d_[p_++])) return false; break; }
+        case BINBYTES: { if (!need(4)) return false; uint32_t k; std::memcpy(&k, d_ + p_, 4); p_ += 4; if (!skip_bytes(k)) return false; break; }
+        case BINBYTES8: { if (!need(8)) return false; uint64_t k; std::memcpy(&k, d_ + p_, 8); p_ += 8; if (!skip_bytes(k)) return false; break; }
+        case TUPLE1: case TUPLE2: case TUPLE3: if (!make_tuple(size_t(op - TUPLE1) + 1)) return false; break;
+        case TUPLE_: {
+          if (nmarks_ == 0) return false;
+          const size_t m = marks_[--nmarks_];
+          if (m > h_ || !make_tuple(h_ - m)) return false;
+          break;
+        }
+        case LIST_: case DICT_: {   // mark .. top -> one opaque value
+          if (nmarks_ == 0) return false;
+          const size_t m = marks_[--nmarks_];
+          if (m > h_ || m == 0) return false;
+          h_ = m;
+          if (!push(Light(Light::OTHER))) return false;
+          break;
+        }
+        case SETITEM:
+          if (h_ < 3 || floor() > h_ - 3) return false;
+          if (h_ == 3 && st_[0].kind == Light::ROOT && !pair(st_[1], st_[2])) return false;
+          h_ -= 2;
+          break;
+        case SETITEMS: {
+          if (nmarks_ == 0) return false;
+          const size_t m = marks_[--nmarks_];
+          if (m > h_ || m == 0 || floor() > m - 1 || (h_ - m) % 2 != 0) return false;
+          if (m == 1 && st_[0].kind == Light::ROOT)
+            for (size_t i = m; i + 1 < h_; i += 2)
+              if (!pair(st_[i], st_[i + 1])) return false;
+          h_ = m;
+          break;
+        }
+        case APPEND:
+          if (h_ < 2 || floor() > h_ - 2 || st_[h_ - 2].kind == Light::ROOT) return false;
+          h_ -= 1;
+          break;
+        case APPENDS: case ADDITEMS: {
+          if (nmarks_ == 0) return false;
+          const size_t m = marks_[--nmarks_];
+          if (m > h_ || m == 0 || floor() > m - 1 || st_[m - 1].kind == Light::ROOT) return false;
+          h_ = m;
+          break;
+        }
+        case MEMOIZE: if (h_ == 0) return false; break;
+        case BINPUT: if (h_ == 0 || !need(1)) return false; p_ += 1; break;
+        case LONG_BINPUT: if (h_ == 0 || !need(4)) return false; p_ += 4; break;
+        case STACK_GLOBAL: case REDUCE:   // two values -> one opaque value
+          if (h_ < 2 || floor() > h_ - 2 || st_[h_ - 2].kind == Light::ROOT) return false;
+          h_ -= 2;
+          if (!push(Light(Light::OTHER))) return false;
+          break;
+        case BUILD:
+          if (h_ < 2 || floor() > h_ - 2 || st_[h_ - 2].kind == Light::ROOT) return false;
+          h_ -= 1;
+          st_[h_ - 1] = Light(Light::OTHER);
+          break;
+        default: return false;   // memo reads, text opcodes, objects: parse() decides
+      }
+    }
+    return false;   // no STOP
+  }
+
+ private:
+  static constexpr size_t kStack = 96, kMarks = 16, kArena = 192;
+  bool need(size_t k) const { return k <= n_ - p_; }
+  // values below the innermost mark belong to an enclosing construct
+  size_t floor() const { return nmarks_ ? marks_[nmarks_ - 1] : 0; }
+  bool push(const Light& v) {
+    if (h_ == kStack) return false;
+    st_[h_++] = v;
+    return true;
+  }
+  bool push_int(int64_t x) {
+    Light v(Light::INT);
+    v.i = x;
+    return push(v);
+  }
+  bool push_str(size_t k) {
+    if (!need(k)) return false;
+    Light v(Light::STR);
+    v.s.p = reinterpret_cast<const char*>(d_ + p_), v.s.n = k;
+    p_ += k;
+    return push(v);
+  }
+  bool skip_bytes(uint64_t k) {
+    if (k > n_ - p_) return false;
+    p_ += size_t(k);
+    return push(Light(Light::OTHER));
+  }
+  bool make_tuple(size_t k) {
+    if (k > h_ || floor() > h_ - k || narena_ + k > kArena) return false;
+    Light v(Light::TUPLE);
+    v.kid0 = uint16_t(narena_), v.nkids = uint16_t(k);
+    for (size_t i = 0; i < k; ++i) {
+      if (st_[h_ - k + i].kind == Light::ROOT) return false;
+      arena_[narena_++] = st_[h_ - k + i];
+    }
+    h_ -= k;
+    return push(v);
+  }
+  // one (key, value) of the top-level dict
+  bool pair(const Light& k, const Light& v) {
+    if (k.kind != Light::STR) return true;   // parse() keeps such pairs; nobody looks them up
+    if (k.s.is(image_key_)) return false;    // an image of its own: the inline path
+    if (k.s.is("btid")) {
+      if (out_->has_btid || v.kind != Light::INT) return false;
+      out_->has_btid = true, out_->btid = v.i;
+    } else if (k.s.is("origin")) {
+      if (out_->has_origin || v.kind != Light::STR) return false;
+      out_->has_origin = true, out_->origin = v.s;
+    } else if (k.s.is("_btshm")) {
+      if (seen_shm_ || v.kind != Light::TUPLE || v.nkids < 8 || v.nkids > 10) return false;
+      seen_shm_ = true;
+      const Light* e = &arena_[v.kid0];
+      if (e[0].kind != Light::STR || e[6].kind != Light::STR || e[7].kind != Light::INT) return false;
+      for (int i = 1; i <= 5; ++i)
+        if (e[i].kind != Light::INT) return false;
+      out_->segment = e[0].s, out_->image_key = e[6].s;
+      out_->slot = e[1].i, out_->offset = e[2].i, out_->h = e[3].i, out_->w = e[4].i, out_->c = e[5].i;
+      out_->gen = e[7].i;
+      out_->elems = v.nkids;
+      if (v.nkids >= 9 && e[8].kind == Light::TUPLE) {
+        const Light* t = &arena_[e[8].kid0];
+        const int tn = e[8].nkids;
+        if (tn == 1 && t[0].kind == Light::STR) {
+          out_->tag0 = t[0].s;
+        } else if (tn == 3 && t[0].kind == Light::STR && t[1].kind == Light::STR && t[2].kind == Light::INT) {
+          out_->tag0 = t[0].s, out_->tag1 = t[1].s, out_->tag2 = t[2].i;
+        } else {
+          return false;
+        }
+        out_->tag_elems = tn;
+      }
+      if (v.nkids == 10) {
+        if (e[9].kind != Light::TUPLE || e[9].nkids != 5) return false;
+        const Light* t = &arena_[e[9].kid0];
+        for (int i = 0; i < 5; ++i) {
+          if (t[i].kind != Light::INT) return false;
+          out_->delta[i] = t[i].i;
+        }
+        out_->has_delta = true;
+      }
+    }
+    return true;
+  }
+
+  const uint8_t* d_;
+  size_t n_, p_ = 0;
+  const char* image_key_;
+  DescriptorScan* out_;
+  Light st_[kStack];
+  size_t h_ = 0;
+  size_t marks_[kMarks];
+  size_t nmarks_ = 0;
+  Light arena_[kArena];
+  size_t narena_ = 0;
+  bool root_made_ = false, seen_shm_ = false;
+};
+
+}  // namespace
+
+bool scan_descriptor(const uint8_t* data, size_t n, const char* image_key, DescriptorScan* out) {
+  *out = DescriptorScan();
+  if (!data || n == 0) return false;
+  DescriptorScanner s(data, n, image_key ? image_key : "", out);
+  if (s.run()) return true;
+  *out = DescriptorScan();
+  return false;
+}
+
 std::string describe(const Value& v) {
   std::ostringstream o;
   switch (v.kind) {

@@ -15,6 +15,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -89,6 +90,45 @@ struct Value {
 
 // Parses a pickle; throws Unsupported on unknown constructs.
 VPtr parse(const uint8_t* data, size_t n);
+
+// --------------------------------------------------------------------------
+// Descriptor scan
+// --------------------------------------------------------------------------
+// What the GPU loader's worker needs of a shared-memory descriptor message
+// ({'btid': .., 'xy': .., '_btshm': (segment, slot, offset, H, W, C, key,
+// generation[, tag[, delta]])}, see csrc/sim/cubesim.cpp), found in one pass
+// over the opcodes with no heap allocation: parse() builds ~40 shared nodes
+// for such a message, and the worker reads three of its entries.  Strings
+// are spans of the message.
+struct Span {
+  const char* p = nullptr;
+  size_t n = 0;
+  bool is(const char* s) const { return n == std::char_traits<char>::length(s) && std::memcmp(p, s, n) == 0; }
+  std::string str() const { return std::string(p ? p : "", n); }
+};
+struct DescriptorScan {
+  Span segment, image_key;        // elements 0 and 6
+  int64_t slot = 0, offset = 0, h = 0, w = 0, c = 0, gen = 0;   // elements 1..5 and 7
+  int elems = 0;                  // elements in the tuple (8..10)
+  // element 8 when it is a tuple (a non-tuple, e.g. None, means "no tag"):
+  // ('rgb_a',) or ('tile16', key segment, key generation)
+  int tag_elems = 0;              // 0: no tag tuple
+  Span tag0, tag1;                // its leading strings (tag1: 3-element tags)
+  int64_t tag2 = 0;               // its third element (3-element tags)
+  bool has_delta = false;         // element 9 is a tuple of 5 integers ...
+  int64_t delta[5] = {0, 0, 0, 0, 0};   // ... (base_gen, y0, y1, x0, x1)
+  bool has_origin = false;
+  Span origin;                    // 'origin' entry (a str)
+  bool has_btid = false;
+  int64_t btid = 0;               // 'btid' entry (a plain int)
+};
+// True when `data` is a well-formed pickle of a dict with a `_btshm` entry of
+// the shapes above and every entry the scan reports has the plain type given
+// there.  False for anything else -- another structure, opcodes the scan does
+// not model (memo reads, protocol-2 text), a truncated or malformed stream,
+// a message with an `image_key` entry of its own -- and the caller then takes
+// parse().  Never reads outside [data, data + n); never throws.
+bool scan_descriptor(const uint8_t* data, size_t n, const char* image_key, DescriptorScan* out);
 
 // Render a value tree as a short human readable string (tests/debug).
 std::string describe(const Value& v);

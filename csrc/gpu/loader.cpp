@@ -222,12 +222,36 @@ std::chrono::microseconds poll_grain() {
   }();
   return std::chrono::microseconds(us);
 }
+// How long a wait on the critical path polls before it sleeps (loader.h).
+// Only a loader configured for the direct path polls: there a launch is a
+// ~76 us kernel and a 60 us sleep is most of it.  A copy-path loader
+// (direct = false) is bound by its DMA copies, ~270 us per batch; polling
+// bought it no throughput and cost 15 CPU-us per frame, so it sleeps at
+// once as before (profiles/r11/feed.md).
+double spin_ms(const LoaderConfig& cfg) {
+  static const double ms = [] {
+    const char* e = std::getenv("BT_LOADER_SPIN_US");
+    const long v = e ? std::atol(e) : 150;
+    return double(std::max(0L, std::min(v, 10000L))) * 1e-3;
+  }();
+  return cfg.direct ? ms : 0.0;
+}
+inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#else
+  std::this_thread::yield();
+#endif
+}
 }  // namespace
 
 StreamLoader::~StreamLoader() { stop(); }
 
 void StreamLoader::start() {
   if (worker_.joinable()) return;
+  done_events_ = std::make_shared<EventPool>(completion_event_flags());
+  post_events_ = std::make_shared<EventPool>(unsigned(hipEventDisableTiming));
+  time_events_ = std::make_shared<EventPool>(unsigned(hipEventDefault));
   worker_ = std::thread([this] {
     pthread_setname_np(pthread_self(), "bt-loader");
     worker_tid_ = int64_t(syscall(SYS_gettid));
@@ -255,7 +279,7 @@ bool StreamLoader::wait_shape(long timeout_ms, int* H, int* W, int* C) {
 void StreamLoader::post(void* dst, hipStream_t consumer) {
   DeviceGuard g(cfg_.device);
   hipEvent_t ev;
-  check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+  check(post_events_ ? post_events_->take(&ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
   check(hipEventRecord(ev, consumer), "hipEventRecord(post)");
   {
     std::lock_guard<std::mutex> lk(mu_);
@@ -279,6 +303,7 @@ bool StreamLoader::next(ReadyBatch* out, hipStream_t consumer, long timeout_ms) 
   }
   *out = std::move(ready_.front());
   ready_.pop_front();
+  first_taken_ = true;
   lk.unlock();
   if (out->done) {   // host_sync = false: the consumer stream waits on the device
     DeviceGuard g(cfg_.device);
@@ -323,13 +348,18 @@ void StreamLoader::promote_ready() {
     unready_.pop_front();
     any = true;
   }
+  if (any) last_progress_ms_ = now_ms();
   if (any) cv_.notify_all();
 }
 
 void StreamLoader::host_wait(hipEvent_t ev) {
-  while (hipEventQuery(ev) == hipErrorNotReady && !stop_) {
+  if (hipEventQuery(ev) != hipErrorNotReady) return;
+  const double spin_end = now_ms() + spin_ms(cfg_);
+  while (!stop_) {
     promote_ready();
-    std::this_thread::sleep_for(std::chrono::microseconds(20));
+    if (hipEventQuery(ev) != hipErrorNotReady) return;
+    if (now_ms() < spin_end) cpu_relax();
+    else std::this_thread::sleep_for(std::chrono::microseconds(20));
   }
 }
 
@@ -427,6 +457,17 @@ void StreamLoader::drain_sockets() {
 void StreamLoader::release_descriptor(const zmtp::Message& m) {
   if (m.size() != 1) return;
   try {
+    codec::DescriptorScan sc;
+    if (codec::scan_descriptor(m[0].data(), m[0].size, cfg_.image_key.c_str(), &sc)) {
+      auto it = segments_.find(std::string_view(sc.segment.p, sc.segment.n));
+      if (it != segments_.end()) {
+        it->second.seg->release(uint32_t(sc.slot), uint32_t(sc.gen));
+      } else {
+        std::unique_ptr<shm::Segment> seg(shm::Segment::open(sc.segment.str()));
+        seg->release(uint32_t(sc.slot), uint32_t(sc.gen));
+      }
+      return;
+    }
     codec::VPtr root = codec::parse(m[0].data(), m[0].size);
     if (!root || root->kind != codec::Value::DICT) return;
     const codec::Value* d = root->get("_btshm");
@@ -447,6 +488,10 @@ void StreamLoader::release_descriptor(const zmtp::Message& m) {
 LoaderStats StreamLoader::stats() {
   std::lock_guard<std::mutex> lk(mu_);
   LoaderStats s = stats_;
+  {
+    std::lock_guard<std::mutex> tk(tally_mu_);   // frames received since the last launch
+    tally_.add_to(s);
+  }
   s.cpu_poll_ms = double(cpu_ns_[kCpuPoll].load()) * 1e-6;
   s.cpu_recv_ms = double(cpu_ns_[kCpuRecv].load()) * 1e-6;
   s.cpu_launch_ms = double(cpu_ns_[kCpuLaunch].load()) * 1e-6;
@@ -495,8 +540,12 @@ void StreamLoader::run() {
       trace::Range tp("btn.loader.poll");
       ev = zmtp::Socket::poll(items, inflight_.empty() && pending_.empty() && unready_.empty() ? 100 : (unready_.empty() ? 1 : 0),
                               intr);
-      if (!unready_.empty() && std::none_of(ev.begin(), ev.end(), [](int e) { return e != 0; }))
-        std::this_thread::sleep_for(poll_grain());   // nothing to receive: poll completions
+      if (!unready_.empty() && std::none_of(ev.begin(), ev.end(), [](int e) { return e != 0; })) {
+        // nothing to receive: poll completions -- back to back for a while
+        // after the last frame or hand-off, then at the sleep grain
+        if (now_ms() - last_progress_ms_ < spin_ms(cfg_)) cpu_relax();
+        else std::this_thread::sleep_for(poll_grain());
+      }
     } catch (const zmtp::Error& e) {
       if (e.code == zmtp::E_INTR) break;
       throw;
@@ -519,6 +568,10 @@ void StreamLoader::run() {
       round.clear();
       if (zmtp::Socket::recv_round(ready, round, room) == 0) break;
       woke += round.size();
+      last_progress_ms_ = now_ms();
+      // a launch that finished meanwhile goes to the consumer now, not after
+      // the up to 64 frames of this wake-up
+      if (!unready_.empty()) promote_ready();
       for (auto& m : round) {
         if (stop_) {
           release_descriptor(m);   // the stream failed / stopped mid-round: hand its shm slot back
@@ -569,21 +622,77 @@ bool StreamLoader::process(zmtp::Message&& msg) {
   const uint8_t* data = it.frame.data();
   const size_t n = it.frame.size;
   codec::VPtr root;
-  try {
-    root = codec::parse(data, n);
-  } catch (const std::exception& e) {
-    return bad(std::string("unparseable pickle (") + e.what() + ")");
+  // A raw or rgb_a shared-memory descriptor -- every frame of the flagship
+  // stream -- is scanned for the three entries the worker reads; its tree is
+  // built later by the thread that reads the metadata (BatchMeta::get_tree).
+  // Everything else (inline images, tile16 frames, protocol-2 pickles, any
+  // shape the scan does not model) is parsed here as before.
+  codec::DescriptorScan sc;
+  const bool scanned = codec::scan_descriptor(data, n, cfg_.image_key.c_str(), &sc) && sc.tag_elems <= 1;
+  if (!scanned) {
+    try {
+      root = codec::parse(data, n);
+    } catch (const std::exception& e) {
+      return bad(std::string("unparseable pickle (") + e.what() + ")");
+    }
+    if (!root || root->kind != codec::Value::DICT) return bad("payload is not a dict");
   }
-  if (!root || root->kind != codec::Value::DICT) return bad("payload is not a dict");
   size_t img_idx = size_t(-1), shm_idx = size_t(-1);
-  for (size_t i = 0; i + 1 < root->items.size(); i += 2) {
+  for (size_t i = 0; root && i + 1 < root->items.size(); i += 2) {
     if (root->items[i]->kind != codec::Value::STR) continue;
     if (root->items[i]->s == cfg_.image_key) img_idx = i;
     else if (root->items[i]->s == "_btshm") shm_idx = i;
   }
   int h, w, c;
   size_t cut = 0, len = 0;
-  if (shm_idx != size_t(-1)) {
+  if (scanned) {
+    // the same checks, in the same order, as the parsed descriptor below
+    uint8_t* dev_base = nullptr;
+    try {
+      MappedSegment& ms = segment(std::string_view(sc.segment.p, sc.segment.n));
+      it.seg = ms.seg.get();
+      it.ms = &ms;
+      dev_base = ms.dev_base;
+    } catch (const std::exception& e) {
+      return bad(e.what());
+    }
+    it.slot = uint32_t(sc.slot);
+    it.gen = uint32_t(sc.gen);
+    const int64_t off = sc.offset;
+    h = int(sc.h), w = int(sc.w), c = int(sc.c);
+    const bool has_codec = sc.tag_elems == 1;
+    if (it.slot >= it.seg->nslots() || off < 0 || (!has_codec && size_t(off) + size_t(h) * w * c > it.seg->size()))
+      return bad("_btshm descriptor out of range");
+    if (!it.seg->claim(it.slot, it.gen)) {
+      std::lock_guard<std::mutex> lk(mu_);
+      stats_.shm_stale++;
+      return false;
+    }
+    guard.armed = true;
+    it.src = it.seg->base() + off;
+    if (dev_base) it.dsrc = dev_base + off;
+    if (sc.has_delta) {
+      const int64_t lim = int64_t(1) << 20;
+      bool ok = true;
+      for (size_t k = 1; ok && k < 5; ++k) ok = sc.delta[k] >= -lim && sc.delta[k] <= lim;
+      if (ok) {
+        it.delta.base_gen = uint32_t(sc.delta[0]);
+        it.delta.rect.y0 = int(sc.delta[1]), it.delta.rect.y1 = int(sc.delta[2]);
+        it.delta.rect.x0 = int(sc.delta[3]), it.delta.rect.x1 = int(sc.delta[4]);
+        ok = mirror::delta_valid(it.delta, h, w);
+      }
+      if (!ok) return bad("malformed _btshm delta");
+      it.has_delta = true;
+    }
+    if (has_codec && sc.tag0.is(planar::kName)) {
+      const size_t slot_lo = it.seg->slot_offset(it.slot);
+      if (c != 4 || size_t(off) < slot_lo || !planar::rgb_a_valid(h, w, off, slot_lo + it.seg->slot_bytes()))
+        return bad("_btshm rgb_a frame out of range");
+      it.planar = true;
+    } else if (has_codec) {
+      return bad("unknown _btshm codec");
+    }
+  } else if (shm_idx != size_t(-1)) {
     // descriptor (segment, slot, byte offset, H, W, C, key): image in shared memory
     const codec::Value& d = *root->items[shm_idx + 1];
     if (d.kind != codec::Value::TUPLE || d.items.size() < 8 || d.items[0]->kind != codec::Value::STR)
@@ -692,7 +801,9 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     }
   }
   if (c < 1 || c > 4) return bad("image channels must be 1..4");
-  if (const codec::Value* o = root->get("origin"))
+  if (scanned)
+    it.flip = sc.has_origin && sc.origin.is("lower-left");
+  else if (const codec::Value* o = root->get("origin"))
     it.flip = o->kind == codec::Value::STR && o->s == "lower-left";
 
   if (!have_shape_) {
@@ -774,6 +885,7 @@ bool StreamLoader::process(zmtp::Message&& msg) {
     shift_offsets(*root, cut, len);
   }
   it.meta.tree = root;
+  it.meta.lazy = scanned;
 
   if (cfg_.jitter) {
     // splitmix64: brightness, contrast, saturation in [max(0, 1 - r), 1 + r], hue in [-r, r] turns
@@ -794,23 +906,34 @@ bool StreamLoader::process(zmtp::Message&& msg) {
   }
   if (cur_.empty()) batch_t0_ = now_ms();
   {
-    std::lock_guard<std::mutex> lk(mu_);
-    stats_.frames++;
-    stats_.bytes += n;
+    // per-frame counts go to the worker's tally (its own lock: next() and
+    // post() never wait behind a frame); launch_group() folds it into stats_
+    // once per launch, and stats() adds what is not folded yet
+    std::lock_guard<std::mutex> lk(tally_mu_);
+    tally_.frames++;
+    tally_.bytes += n;
     if (it.tiled) {
-      stats_.image_bytes += 4 * (size_t(it.ntiles) + 1) + size_t(it.ntiles) * tiledelta::tile_bytes(c);
-      stats_.tiled_frames++;
+      tally_.image_bytes += 4 * (size_t(it.ntiles) + 1) + size_t(it.ntiles) * tiledelta::tile_bytes(c);
+      tally_.tiled_frames++;
     } else if (it.planar) {
       // only the RGB part crosses the link when the frame is read in place;
       // materialize() adds the alpha plane's bytes if it has to rebuild it
-      stats_.image_bytes += size_t(h) * w * 3;
-      stats_.planar_frames++;
+      tally_.image_bytes += size_t(h) * w * 3;
+      tally_.planar_frames++;
     } else {
-      stats_.image_bytes += img_bytes_;
+      tally_.image_bytes += img_bytes_;
     }
-    if (it.seg) stats_.shm_frames++;
-    if (const codec::Value* b = root->get("btid"))
-      if (b->kind == codec::Value::INT) stats_.frames_per_btid[b->i]++;
+    if (it.seg) tally_.shm_frames++;
+    bool has_btid = scanned && sc.has_btid;
+    int64_t btid = sc.btid;
+    if (!scanned)
+      if (const codec::Value* b = root->get("btid"))
+        if (b->kind == codec::Value::INT) has_btid = true, btid = b->i;
+    if (has_btid) {
+      auto e = std::find_if(tally_.btid.begin(), tally_.btid.end(), [&](const auto& kv) { return kv.first == btid; });
+      if (e == tally_.btid.end()) tally_.btid.emplace_back(btid, 1);
+      else e->second++;
+    }
   }
   guard.armed = false;
   cur_.push_back(std::move(it));
@@ -888,9 +1011,10 @@ void StreamLoader::materialize(Item& it, bool keep_planar) {
   it.key = nullptr;
 }
 
-StreamLoader::MappedSegment& StreamLoader::segment(const std::string& name) {
-  auto it = segments_.find(name);
+StreamLoader::MappedSegment& StreamLoader::segment(std::string_view name_view) {
+  auto it = segments_.find(name_view);
   if (it != segments_.end()) return it->second;
+  const std::string name(name_view);
   MappedSegment ms;
   ms.seg.reset(shm::Segment::open(name));
   // pin + map the producer's ring: the DMA engine (copy path) or the decode
@@ -982,14 +1106,23 @@ void StreamLoader::reap(bool wait_all) {
     f.copied.reset();
     if (f.t0) {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, f.t0, f.t1) == hipSuccess) {
+      // t1 is recorded behind `copied` (direct path: right behind it; copy
+      // path: behind the kernel that follows the copies), so a worker that
+      // polls `copied` can be here before t1 completes: wait for it instead
+      // of losing the sample
+      hipError_t te = hipEventElapsedTime(&ms, f.t0, f.t1);
+      if (te == hipErrorNotReady) {
+        (void)hipEventSynchronize(f.t1);
+        te = hipEventElapsedTime(&ms, f.t0, f.t1);
+      }
+      if (te == hipSuccess) {
         std::lock_guard<std::mutex> lk(mu_);
         stats_.timed_launches++;
         stats_.timed_images += uint64_t(f.images);
         stats_.timed_gpu_ms += ms;
       }
-      (void)hipEventDestroy(f.t0);
-      (void)hipEventDestroy(f.t1);
+      time_events_->give(f.t0);
+      time_events_->give(f.t1);
     }
     uint64_t torn = 0;
     for (auto& s : f.slots) {
@@ -1045,7 +1178,23 @@ void StreamLoader::launch() {
   Posted p{nullptr, nullptr};
   {
     std::unique_lock<std::mutex> lk(mu_);
+    const double t_enter = posted_.empty() ? now_ms() : 0.0;
+    const double spin_end = t_enter + spin_ms(cfg_);
+    // Start of the stream only: until the consumer has taken its first batch
+    // it may still be handing over its first buffers (one device allocation
+    // each), which is not being out of them.  The worker assembles a batch in
+    // a few tens of microseconds now, less than such a post takes, so batches
+    // held for coalescing wait up to this long for the next post (asleep on
+    // the condition variable post() signals) before they are flushed; with
+    // launch_depth = 0 the first 64 images otherwise went out in two launches
+    // about one time in four (tests/test_gpu_loader.py: coalesced_launch).
+    // After the first hand-out an empty posted_ flushes at once, as before.
+    constexpr double kPostGraceMs = 0.3;
     while (posted_.empty() && !stop_) {
+      if (!first_taken_ && !pending_.empty() && now_ms() - t_enter < kPostGraceMs) {
+        cv_.wait_for(lk, std::chrono::microseconds(50));
+        continue;
+      }
       lk.unlock();
       // out of output buffers: the consumer is waiting for batches, so
       // holding assembled ones back for coalescing would only stall it
@@ -1053,6 +1202,14 @@ void StreamLoader::launch() {
       promote_ready();
       lk.lock();
       if (!posted_.empty() || stop_) break;
+      if (now_ms() < spin_end) {
+        // the buffer is usually a hand-off away (the consumer posts one for
+        // every batch it takes): look again at once before sleeping
+        lk.unlock();
+        cpu_relax();
+        lk.lock();
+        continue;
+      }
       if (!unready_.empty()) {
         // the consumer is most likely waiting for one of these: keep
         // promoting at a fine grain instead of sleeping through a post
@@ -1177,9 +1334,15 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   const bool plain = direct && !cfg_.color_matrix && !group.front().tiled;
   const hipStream_t st = plain ? next_decode_stream() : stream_;
   for (auto& b : group) {
-    if (cfg_.host_sync) host_wait(b.ready);   // the consumer is done with the buffer
-    else check(hipStreamWaitEvent(st, b.ready, 0), "hipStreamWaitEvent(post)");
-    (void)hipEventDestroy(b.ready);
+    if (cfg_.host_sync) {
+      host_wait(b.ready);   // the consumer is done with the buffer
+      if (!stop_) post_events_->give(b.ready);   // seen complete: nothing waits on it any more
+      else (void)hipEventDestroy(b.ready);
+    } else {
+      check(hipStreamWaitEvent(st, b.ready, 0), "hipStreamWaitEvent(post)");
+      (void)hipEventDestroy(b.ready);
+    }
+    b.ready = nullptr;
     total += int(b.items.size());
   }
   const size_t elem = cfg_.color_matrix ? 4 : (cfg_.out_dtype == OUT_F32 ? 4 : (cfg_.out_dtype == OUT_U8 ? 1 : 2));
@@ -1201,10 +1364,12 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   const int64_t launch_no = ++launch_no_;
   // skip the cold first launches (allocation, code-object load, page faults)
-  if (launch_no > kTimedSkip && launch_no % kTimedEvery == 0 && hipEventCreate(&t0) == hipSuccess) {
-    if (hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, st) != hipSuccess) {
-      (void)hipEventDestroy(t0);
-      if (t1) (void)hipEventDestroy(t1);
+  if (launch_no > kTimedSkip) untimed_images_ += total;
+  if (untimed_images_ >= kTimedEveryImages && time_events_->take(&t0) == hipSuccess) {
+    untimed_images_ = 0;
+    if (time_events_->take(&t1) != hipSuccess || hipEventRecord(t0, st) != hipSuccess) {
+      time_events_->give(t0);
+      if (t1) time_events_->give(t1);
       t0 = t1 = nullptr;
     }
   }
@@ -1213,9 +1378,10 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   const bool passthrough = !direct && passthrough_ &&
                            std::none_of(all.begin(), all.end(), [](const Item* it) { return it->flip; });
   auto copied = std::make_shared<EventSet>();
+  copied->pool = done_events_;
   auto add_event = [&](hipStream_t st) {
     hipEvent_t ev;
-    check(hipEventCreateWithFlags(&ev, completion_event_flags()), "hipEventCreate(copied)");
+    check(done_events_->take(&ev), "hipEventCreate(copied)");
     check(hipEventRecord(ev, st), "hipEventRecord(copied)");
     copied->ev.push_back(ev);
   };
@@ -1478,8 +1644,8 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     check(hipEventRecord(stage_free_[stage_idx], stream_), "hipEventRecord(stage)");
   }
   if (t0 && host_passthrough) {   // the copies ran on other streams: nothing on stream_ to time
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
+    time_events_->give(t0);
+    time_events_->give(t1);
     t0 = t1 = nullptr;
   }
   if (t0) check(hipEventRecord(t1, st), "hipEventRecord(t1)");
@@ -1513,8 +1679,9 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       rb.pending = copied;
     } else if (cfg_.host_sync) {
       auto fin = std::make_shared<EventSet>();
+      fin->pool = done_events_;
       hipEvent_t ev;
-      check(hipEventCreateWithFlags(&ev, completion_event_flags()), "hipEventCreate(done)");
+      check(done_events_->take(&ev), "hipEventCreate(done)");
       check(hipEventRecord(ev, st), "hipEventRecord(done)");
       fin->ev.push_back(ev);
       rb.pending = fin;
@@ -1529,6 +1696,11 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   inflight_.push_back(std::move(fl));
   {
     std::lock_guard<std::mutex> lk(mu_);
+    {
+      std::lock_guard<std::mutex> tk(tally_mu_);
+      tally_.add_to(stats_);
+      tally_.clear();
+    }
     stats_.batches += group.size();
     stats_.launches++;
     if (direct) stats_.direct_batches += group.size();

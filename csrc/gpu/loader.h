@@ -41,6 +41,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <vector>
 
@@ -198,17 +199,90 @@ struct LoaderConfig {
 struct BatchMeta {
   std::vector<uint8_t> bytes;        // frame with the image payload cut out
   codec::VPtr tree;                  // parse tree over `bytes` (image entry removed)
+  // A shared-memory descriptor the worker only scanned (codec::scan_descriptor)
+  // has no tree yet: it is built here, by whoever reads the metadata (the
+  // consumer's thread), without the `_btshm` entry.  Throws what the worker
+  // would have reported for a message parse() rejects.
+  // A change of behaviour for such a message: the scan does not look into the
+  // values it skips (an ndarray's dtype, say), so a descriptor message whose
+  // other entries parse() rejects used to be counted `bad` on the worker and
+  // dropped under skip_bad; now its frame is decoded and counted, and the
+  // error surfaces here, from next(), where skip_bad cannot drop one image
+  // out of a decoded batch.  cubesim and the Python publisher write no such
+  // message.
+  bool lazy = false;
+  const codec::VPtr& get_tree() {
+    if (lazy && !tree) {
+      try {
+        tree = codec::parse(bytes.data(), bytes.size());
+      } catch (const std::exception& e) {
+        throw std::runtime_error(std::string("StreamLoader: bad message: unparseable pickle (") + e.what() + ")");
+      }
+      if (tree && tree->kind == codec::Value::DICT)
+        for (size_t i = 0; i + 1 < tree->items.size(); i += 2)
+          if (tree->items[i]->kind == codec::Value::STR && tree->items[i]->s == "_btshm") {
+            tree->items.erase(tree->items.begin() + long(i), tree->items.begin() + long(i) + 2);
+            break;
+          }
+      lazy = false;
+    }
+    return tree;
+  }
+};
+
+// Free list of events of one flag set.  A launch used to create, record and
+// destroy its events; a recorded event that nobody waits for any more is
+// simply recorded again.  take() and give() may come from any thread (the
+// last owner of an EventSet can be the consumer's).
+class EventPool {
+ public:
+  explicit EventPool(unsigned flags) : flags_(flags) {}
+  EventPool(const EventPool&) = delete;
+  EventPool& operator=(const EventPool&) = delete;
+  ~EventPool() {
+    for (auto e : free_) (void)hipEventDestroy(e);
+  }
+  hipError_t take(hipEvent_t* ev) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (!free_.empty()) {
+        *ev = free_.back();
+        free_.pop_back();
+        return hipSuccess;
+      }
+    }
+    created_++;
+    return hipEventCreateWithFlags(ev, flags_);
+  }
+  void give(hipEvent_t ev) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (free_.size() < kKeep) free_.push_back(ev);
+    else (void)hipEventDestroy(ev);
+  }
+  uint64_t created() const { return created_.load(); }
+  static constexpr size_t kKeep = 32;   // more than are ever in flight (launch depth, posted buffers)
+
+ private:
+  const unsigned flags_;
+  std::mutex mu_;
+  std::vector<hipEvent_t> free_;
+  std::atomic<uint64_t> created_{0};
 };
 
 // Events owned jointly by an in-flight launch (slot release) and the batches
-// waiting for completion (host_sync); destroyed with the last owner.
+// waiting for completion (host_sync); they go back to their pool (or are
+// destroyed) with the last owner.
 struct EventSet {
   std::vector<hipEvent_t> ev;
+  std::shared_ptr<EventPool> pool;   // where the events go back to (null: destroyed)
   EventSet() = default;
   EventSet(const EventSet&) = delete;
   EventSet& operator=(const EventSet&) = delete;
   ~EventSet() {
-    for (auto e : ev) (void)hipEventDestroy(e);
+    for (auto e : ev) {
+      if (pool) pool->give(e);
+      else (void)hipEventDestroy(e);
+    }
   }
   // all complete? (errors count as complete: the stream reports them later)
   bool done() const {
@@ -249,8 +323,9 @@ struct LoaderStats {
   uint64_t delta_frames = 0;               // frames of which only the reported region was read from the host
   uint64_t mirror_bytes = 0;               // HBM held by slot mirrors
   double h2d_issue_ms = 0;
-  // GPU time of every kTimedEvery-th launch (timing events around its H2D
-  // copies + decode kernel): per-image device cost without timing every launch
+  // GPU time of one launch per kTimedEveryImages images (timing events around
+  // its H2D copies + decode kernel): per-image device cost without timing
+  // every launch
   uint64_t timed_launches = 0, timed_images = 0;
   double timed_gpu_ms = 0;
   uint64_t keys_evicted = 0;               // replaced tile16 key frames freed from HBM
@@ -375,8 +450,20 @@ class StreamLoader {
   std::deque<Pending> pending_;
   int pending_images_ = 0;
   static constexpr int kMaxDecodeStreams = 4;
-  static constexpr int kTimedEvery = 4;
+  // a launch is timed once this many images went out since the last timed one
+  // (sampling by images: with one batch per launch a per-launch rule fires
+  // several times as often as with coalesced launches)
+  static constexpr int kTimedEveryImages = 96;
   static constexpr int kTimedSkip = 8;         // cold launches never sampled
+  int64_t untimed_images_ = 0;
+  // reused events: completion markers, the consumer's post events, timing pairs
+  std::shared_ptr<EventPool> done_events_, post_events_, time_events_;
+  // Waiting on the critical path (a posted buffer's event, the oldest launch,
+  // a buffer to launch into) first polls for a bounded time and only then
+  // sleeps: a sleep of 10-20 us returns after ~60 us under the default timer
+  // slack, most of a decode kernel's run time.  BT_LOADER_SPIN_US (default
+  // 150, 0: sleep at once) bounds each such wait's polling.  Loaders
+  // configured for the copy path (direct = false) do not poll.
   static constexpr int64_t kKeyIdleLaunches = 64;
   int64_t launch_no_ = 0, retired_launch_ = 0;
   double last_reap_ms_ = 0;
@@ -425,8 +512,8 @@ class StreamLoader {
   void invalidate_mirror(shm::Segment* seg, uint32_t slot);
   std::map<const shm::Segment*, MappedSegment*> by_seg_;
   mirror::Budget mirror_budget_;
-  MappedSegment& segment(const std::string& name);
-  std::map<std::string, MappedSegment> segments_;   // mapped + hipHostRegister'ed
+  MappedSegment& segment(std::string_view name);
+  std::map<std::string, MappedSegment, std::less<>> segments_;   // mapped + hipHostRegister'ed
   struct KeyFrame {
     std::unique_ptr<shm::Segment> seg;
     uint8_t* dev = nullptr;          // HBM copy, made on first use
@@ -440,7 +527,26 @@ class StreamLoader {
   std::deque<Inflight> inflight_;   // H2D copies not yet known complete
   int64_t batch_index_ = 0;
   double batch_t0_ = 0;
+  double last_progress_ms_ = 0;     // run(): last frame received or batch handed over
+  bool first_taken_ = false;        // next() has handed out a batch (guarded by mu_)
   LoaderStats stats_;
+  // per-frame counters of process(), folded into stats_ once per launch
+  // (lock order: mu_, then tally_mu_)
+  struct Tally {
+    uint64_t frames = 0, bytes = 0, image_bytes = 0, tiled_frames = 0, planar_frames = 0, shm_frames = 0;
+    std::vector<std::pair<int64_t, uint64_t>> btid;
+    void add_to(LoaderStats& s) const {
+      s.frames += frames, s.bytes += bytes, s.image_bytes += image_bytes;
+      s.tiled_frames += tiled_frames, s.planar_frames += planar_frames, s.shm_frames += shm_frames;
+      for (const auto& kv : btid) s.frames_per_btid[kv.first] += kv.second;
+    }
+    void clear() {
+      frames = bytes = image_bytes = tiled_frames = planar_frames = shm_frames = 0;
+      btid.clear();
+    }
+  };
+  Tally tally_;
+  std::mutex tally_mu_;
 };
 
 }  // namespace gpu

@@ -1384,6 +1384,9 @@ PYBIND11_MODULE(_hip, m) {
              {
                py::gil_scoped_release nogil;
                ok = l.next(&rb, stream_of(stream), timeout_ms);
+               // descriptors the worker only scanned: their trees are built
+               // here, on the consumer's thread and outside the GIL
+               if (ok) for (auto& it : rb.items) it.get_tree();
              }
              if (!ok) return py::none();                 // timeout
              if (rb.index < 0) return py::make_tuple(-1, py::list(), 0.0);   // exhausted
@@ -1402,6 +1405,9 @@ PYBIND11_MODULE(_hip, m) {
              {
                py::gil_scoped_release nogil;
                ok = l.next(&rb, stream_of(stream), timeout_ms);
+               // descriptors the worker only scanned: their trees are built
+               // here, on the consumer's thread and outside the GIL
+               if (ok) for (auto& it : rb.items) it.get_tree();
              }
              if (!ok) return py::none();
              if (rb.index < 0) return py::make_tuple(-1, py::dict(), 0.0);

@@ -2,6 +2,8 @@
 // the pickle codec.  Built as `blendtorch/_native*.so` (no HIP dependency, so
 // it runs in Blender-side producer processes and CPU-only tests as well).
 #include <atomic>
+#include <functional>
+#include <memory>
 #include <pybind11/eval.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -300,6 +302,36 @@ class NativeError(Exception):
       throw py::value_error(std::string("unsupported pickle: ") + e.what());
     }
   });
+  // The GPU loader's one-pass scan of a shared-memory descriptor message
+  // (codec::scan_descriptor): a dict of what it found, or None where the
+  // loader would take the full parse instead.
+  m.def("scan_descriptor", [](py::buffer b, const std::string& image_key) -> py::object {
+    auto info = b.request();
+    const size_t n = size_t(info.size * info.itemsize);
+    // an exactly sized copy: a read past the end is a heap overflow, not a read of the caller's slack
+    std::unique_ptr<uint8_t[]> copy(new uint8_t[n ? n : 1]);
+    if (n) std::memcpy(copy.get(), info.ptr, n);
+    codec::DescriptorScan sc;
+    if (!codec::scan_descriptor(copy.get(), n, image_key.c_str(), &sc)) return py::none();
+    py::dict d;
+    // (bytes that are no UTF-8 -- a corrupted message -- come back as surrogates, not as an exception)
+    auto text = [](const codec::Span& s) {
+      return py::reinterpret_steal<py::object>(PyUnicode_DecodeUTF8(s.p ? s.p : "", py::ssize_t(s.n), "surrogateescape"));
+    };
+    d["segment"] = text(sc.segment);
+    d["slot"] = sc.slot, d["offset"] = sc.offset, d["shape"] = py::make_tuple(sc.h, sc.w, sc.c);
+    d["image_key"] = text(sc.image_key);
+    d["generation"] = sc.gen;
+    d["elements"] = sc.elems;
+    if (sc.tag_elems == 1) d["tag"] = py::make_tuple(text(sc.tag0));
+    else if (sc.tag_elems == 3) d["tag"] = py::make_tuple(text(sc.tag0), text(sc.tag1), sc.tag2);
+    else d["tag"] = py::none();
+    if (sc.has_delta) d["delta"] = py::make_tuple(sc.delta[0], sc.delta[1], sc.delta[2], sc.delta[3], sc.delta[4]);
+    else d["delta"] = py::none();
+    d["origin"] = sc.has_origin ? text(sc.origin) : py::object(py::none());
+    d["btid"] = sc.has_btid ? py::object(py::int_(sc.btid)) : py::object(py::none());
+    return d;
+  }, py::arg("data"), py::arg("image_key") = "image");
   // decode value transform: the cheapest per-channel form that reproduces
   // the fp32 table exactly (codec/xform_fit.h); None when there is none
   m.def("xform_fit",
@@ -352,13 +384,27 @@ class NativeError(Exception):
   m.def("dumps_array_dict",
         [](const py::dict& d, int protocol, size_t align) {
           // Minimal writer used by tests/producers: str keys; values int, float,
-          // str, bool, None or C-contiguous ndarray.
+          // str, bool, None, C-contiguous ndarray, or a tuple of int / str /
+          // None / such tuples (a `_btshm` descriptor, as cubesim writes it).
           codec::Writer w(protocol);
+          std::function<void(py::handle)> tuple_item = [&](py::handle v) {
+            if (v.is_none()) w.none();
+            else if (py::isinstance<py::int_>(v) && !py::isinstance<py::bool_>(v)) w.integer(v.cast<int64_t>());
+            else if (py::isinstance<py::str>(v)) w.str(v.cast<std::string>());
+            else if (py::isinstance<py::tuple>(v)) {
+              w.begin_tuple();
+              for (auto e : py::reinterpret_borrow<py::tuple>(v)) tuple_item(e);
+              w.end_tuple();
+            } else {
+              throw py::type_error("dumps_array_dict: unsupported tuple element");
+            }
+          };
           w.begin_dict();
           for (auto kv : d) {
             w.key(kv.first.cast<std::string>());
             py::handle v = kv.second;
             if (v.is_none()) w.none();
+            else if (py::isinstance<py::tuple>(v)) tuple_item(v);
             else if (py::isinstance<py::bool_>(v)) w.boolean(v.cast<bool>());
             else if (py::isinstance<py::int_>(v)) w.integer(v.cast<int64_t>());
             else if (py::isinstance<py::float_>(v)) w.real(v.cast<double>());

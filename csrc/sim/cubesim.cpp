@@ -277,8 +277,9 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
     }
   }
   std::printf("{\"frames\": %lld, \"full_ms\": %.4f, \"incremental_ms\": %.4f, \"mismatched_bytes\": %lld, "
-              "\"mirror_mismatched_bytes\": %lld, \"checksum\": \"%016llx\"}\n",
-              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, mirror_mismatches, (unsigned long long)h);
+              "\"mirror_mismatched_bytes\": %lld, \"checksum\": \"%016llx\", \"isa\": \"%s\"}\n",
+              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, mirror_mismatches, (unsigned long long)h,
+              sim::raster_isa());
   return mismatches == 0 && mirror_mismatches == 0 ? 0 : 1;
 }
 

@@ -10,8 +10,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <stdexcept>
 
 #include <immintrin.h>
 
@@ -57,6 +59,94 @@ const ToneLut& tone() {
   return t;
 }
 
+// ---- AVX2 fill bodies (raster.h: raster_isa).  Compiled for AVX2 by a
+// target attribute -- the build flags stay -- and called only after the
+// run-time CPU check.  The float operations are the scalar path's, one
+// rounding each (the target has no fused multiply-add), so the bytes agree.
+bool use_avx2() {
+  static const bool on = [] {
+    const bool have = __builtin_cpu_supports("avx2");
+    const char* e = std::getenv("BLENDTORCH_RASTER_ISA");
+    if (e && std::strcmp(e, "scalar") == 0) return false;
+    return have;   // "avx2" on a CPU without it stays scalar
+  }();
+  return on;
+}
+
+// idx[k] = int(clamp(a * (I0 + dI * (kb + k)), 0, 4096)) for k in [0, n)
+// rounded up to 8 (idx: 32-byte aligned, room for that)
+__attribute__((target("avx2"))) void tone_indices_avx2(int* idx, int n, float I0, float dI, float kb, float a) {
+  const __m256 vI0 = _mm256_set1_ps(I0), vdI = _mm256_set1_ps(dI), lo = _mm256_setzero_ps();
+  const __m256 hi = _mm256_set1_ps(4096.f), va = _mm256_set1_ps(a), eight = _mm256_set1_ps(8.f);
+  __m256 kv = _mm256_add_ps(_mm256_set1_ps(kb), _mm256_setr_ps(0.f, 1.f, 2.f, 3.f, 4.f, 5.f, 6.f, 7.f));
+  for (int k = 0; k < n; k += 8, kv = _mm256_add_ps(kv, eight)) {
+    const __m256 I = _mm256_add_ps(vI0, _mm256_mul_ps(vdI, kv));
+    _mm256_store_si256(reinterpret_cast<__m256i*>(idx + k),
+                       _mm256_cvttps_epi32(_mm256_min_ps(_mm256_max_ps(_mm256_mul_ps(va, I), lo), hi)));
+  }
+}
+
+// Grey pixels from gray4[idx[k]], whole groups of 8 only; returns how many
+// pixels were written (a multiple of 8, <= n).  No byte past them is touched.
+__attribute__((target("avx2"))) int store_gray4_avx2(uint8_t* p, const int* idx, int n, const uint32_t* gray4) {
+  int k = 0;
+  for (; k + 8 <= n; k += 8, p += 32) {
+    const __m256i v = _mm256_i32gather_epi32(reinterpret_cast<const int*>(gray4),
+                                             _mm256_load_si256(reinterpret_cast<const __m256i*>(idx + k)), 4);
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(p), v);
+  }
+  return k;
+}
+__attribute__((target("avx2"))) int store_gray3_avx2(uint8_t* p, const int* idx, int n, const uint32_t* gray4) {
+  // per 128-bit lane: 4 RGBA pixels -> 12 bytes of packed RGB, 4 zero bytes
+  const __m256i pack = _mm256_setr_epi8(0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, -1, -1, -1, -1,
+                                        0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, -1, -1, -1, -1);
+  int k = 0;
+  for (; k + 8 <= n; k += 8, p += 24) {
+    __m256i v = _mm256_i32gather_epi32(reinterpret_cast<const int*>(gray4),
+                                       _mm256_load_si256(reinterpret_cast<const __m256i*>(idx + k)), 4);
+    v = _mm256_shuffle_epi8(v, pack);
+    const __m128i l = _mm256_castsi256_si128(v), h = _mm256_extracti128_si256(v, 1);
+    // the 16-byte store's last 4 bytes fall on bytes 12..15 of these 24,
+    // which the two stores of the high half rewrite: 24 bytes in all
+    _mm_storeu_si128(reinterpret_cast<__m128i*>(p), l);
+    _mm_storel_epi64(reinterpret_cast<__m128i*>(p + 12), h);
+    const uint32_t t = uint32_t(_mm_extract_epi32(h, 2));
+    std::memcpy(p + 20, &t, 4);
+  }
+  return k;
+}
+
+// Constant pixels: whole groups only, returns the pixels written (<= n).
+__attribute__((target("avx2"))) int fill_rgba_avx2(uint8_t* p, int n, uint32_t v) {
+  const __m256i pv = _mm256_set1_epi32(int(v));
+  int k = 0;
+  for (; k + 8 <= n; k += 8, p += 32) _mm256_storeu_si256(reinterpret_cast<__m256i*>(p), pv);
+  return k;
+}
+__attribute__((target("avx2"))) int fill_rgb_avx2(uint8_t* p, int n, const uint8_t* pat96) {
+  const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(pat96));
+  const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(pat96 + 32));
+  const __m256i c = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(pat96 + 64));
+  int k = 0;
+  for (; k + 32 <= n; k += 32, p += 96) {   // 96 bytes: 32 pixels, the pattern's period in 32-byte stores
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(p), a);
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(p + 32), b);
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(p + 64), c);
+  }
+  if (k + 16 <= n) {   // 48 bytes: 16 pixels
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(p), a);
+    _mm_storeu_si128(reinterpret_cast<__m128i*>(p + 32), _mm256_castsi256_si128(b));
+    k += 16, p += 48;
+  }
+  if (k + 8 <= n) {    // 24 bytes: 8 pixels
+    _mm_storeu_si128(reinterpret_cast<__m128i*>(p), _mm256_castsi256_si128(a));
+    _mm_storel_epi64(reinterpret_cast<__m128i*>(p + 16), _mm256_extracti128_si256(a, 1));
+    k += 8;
+  }
+  return k;
+}
+
 // Ray/oriented-box overlap for t in (tmin, tmax).
 bool ray_hits_box(const Box& b, const Vec3& o, const Vec3& d, double tmin, double tmax) {
   Vec3 lo = mul_t(b.rot, sub(o, b.center));
@@ -81,6 +171,8 @@ bool ray_hits_box(const Box& b, const Vec3& o, const Vec3& d, double tmin, doubl
 inline double light_scale(const Light& l) { return l.power / (4.0 * kPi * kPi); }
 
 }  // namespace
+
+const char* raster_isa() { return use_avx2() ? "avx2" : "scalar"; }
 
 Mat3 euler_xyz(double rx, double ry, double rz) {
   double cx = std::cos(rx), sx = std::sin(rx), cy = std::cos(ry), sy = std::sin(ry);
@@ -198,6 +290,7 @@ Renderer::Renderer(const Scene& s, int channels, bool lower_left)
   background_.assign(size_t(W_) * H_ * C_, 255);
   plane_xy_.assign(size_t(W_) * H_ * 2, std::numeric_limits<float>::quiet_NaN());
   for (int c = 0; c < 3; ++c) shadow_rgb_[c] = T(s.plane_albedo[c] * s.ambient);
+  for (int i = 0; i < 96; ++i) shadow_pat3_[i] = shadow_rgb_[i % 3];
   for (int y = 0; y < H_; ++y) {
     const double cy = -((y + 0.5) - 0.5 * H_) / f;
     for (int x = 0; x < W_; ++x) {
@@ -295,22 +388,54 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
   const double amb = s.ambient;
   const ToneLut& T = tone();
 
+  const bool avx2 = use_avx2();
   auto row_ptr = [&](int y) { return out + size_t(lower_left_ ? (H - 1 - y) : y) * W * C; };
-  if (dirty && dirty->known) {
+  // background bytes back into pixels [a, b] of image row y
+  auto restore = [&](int y, int a, int b) {
+    uint8_t* r = row_ptr(y);
+    const size_t off = size_t(a) * C;
+    std::memcpy(r + off, background_.data() + (r - out) + off, size_t(b - a + 1) * C);
+  };
+  // restore after draw (raster.h): one box, so every face span is written in
+  // full (no depth test) and a row holds at most 1 + 6 intervals
+  const bool deferred = dirty && dirty->known && !dirty->empty() && dirty->lo.size() == size_t(H) &&
+                        dirty->hi.size() == size_t(H) && s.boxes.size() == 1;
+  const int old_y0 = deferred ? std::max(dirty->y0, 0) : 0, old_y1 = deferred ? std::min(dirty->y1, H - 1) : -1;
+  if (deferred) {
+    prev_lo_.swap(dirty->lo);   // (dirty's arrays become this frame's record below)
+    prev_hi_.swap(dirty->hi);
+    cover_.resize(size_t(H) * kMaxCover * 2);
+    cover_n_.assign(size_t(H), 0);
+  } else if (dirty && dirty->known) {
     // only the previous frame's boxes and shadows differ from the background
     if (!dirty->empty()) {
       const bool rows = dirty->lo.size() == size_t(H);
       for (int y = dirty->y0; y <= dirty->y1; ++y) {
         const int a = rows ? dirty->lo[size_t(y)] : dirty->x0, b = rows ? dirty->hi[size_t(y)] : dirty->x1;
-        if (a > b) continue;
-        uint8_t* r = row_ptr(y);
-        const size_t off = size_t(a) * C;
-        std::memcpy(r + off, background_.data() + (r - out) + off, size_t(b - a + 1) * C);
+        if (a <= b) restore(y, a, b);
       }
     }
   } else {
     std::memcpy(out, background_.data(), background_.size());
   }
+  // deferred: the frame wrote every pixel of [a, b] in row y
+  auto cover = [&](int y, int a, int b) {
+    uint8_t& n = cover_n_[size_t(y)];
+    if (n == kRowRestored) return;
+    if (n >= kMaxCover) throw std::logic_error("raster: more fill intervals in a row than one box can make");
+    int* c = &cover_[(size_t(y) * kMaxCover + n) * 2];
+    c[0] = a, c[1] = b;
+    ++n;
+  };
+  // deferred: a row the intervals cannot describe takes the old order --
+  // restored here, before anything of this frame is drawn into it
+  auto restore_row_first = [&](int y) {
+    uint8_t& n = cover_n_[size_t(y)];
+    if (n == kRowRestored) return;
+    if (y >= old_y0 && y <= old_y1 && prev_lo_[size_t(y)] <= prev_hi_[size_t(y)])
+      restore(y, prev_lo_[size_t(y)], prev_hi_[size_t(y)]);
+    n = kRowRestored;
+  };
   DirtyRect touched;
   if (dirty) {   // reuse the previous record's row arrays (no allocation per frame)
     touched.lo.swap(dirty->lo);
@@ -344,24 +469,33 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
       const float* pxy = &plane_xy_[size_t(y) * W * 2];
       uint8_t* r = row_ptr(y);
       if (plane_dense_[y]) {
-        const int a = std::max(x0, plane_x0_[y]), b = std::min(x1, plane_x1_[y]);
+        int a = std::max(x0, plane_x0_[y]);
+        const int b = std::min(x1, plane_x1_[y]);
+        if (a > b) return;
+        if (deferred) cover(y, a, b);
         if (C == 4) {
           // alpha is 255 in the background: one 32-bit pattern per pixel
           const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
                              uint32_t(shadow_rgb_[2]) << 16 | 0xff000000u;
+          if (avx2) a += fill_rgba_avx2(r + size_t(a) * 4, b - a + 1, v);
           for (int x = a; x <= b; ++x) std::memcpy(r + size_t(x) * 4, &v, 4);
-        } else if (a <= b) {
+        } else {
           // packed RGB: one 32-bit store per pixel as well -- its 4th byte
           // lands on the next pixel's red, which that pixel's store rewrites;
           // the span's last pixel is written as 3 bytes
           const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
                              uint32_t(shadow_rgb_[2]) << 16 | uint32_t(shadow_rgb_[0]) << 24;
+          if (avx2) a += fill_rgb_avx2(r + size_t(a) * 3, b - a + 1, shadow_pat3_);
+          if (a > b) return;
           for (int x = a; x < b; ++x) std::memcpy(r + size_t(x) * 3, &v, 4);
           uint8_t* p = r + size_t(b) * 3;
           p[0] = shadow_rgb_[0], p[1] = shadow_rgb_[1], p[2] = shadow_rgb_[2];
         }
         return;
       }
+      // per-pixel test: no interval to record (one box: this span is the
+      // row's first write of the frame)
+      if (deferred) restore_row_first(y);
       for (int x = x0; x <= x1; ++x) {
         if (pxy[2 * x] != pxy[2 * x]) continue;   // not on the ground plane
         uint8_t* p = r + size_t(x) * C;
@@ -432,6 +566,7 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
           scan_convex(tx, ty, 3, W, H, [&](int y, int x0, int x1) {
             touched.add(y, x0, x1);
             if (need_depth) depth_rect_.add(y, x0, x1);
+            if (deferred) cover(y, x0, x1);
             uint8_t* r = row_ptr(y);
             const double yc = y + 0.5;
             const float I0 = float(ip.a * (x0 + 0.5) + ip.b * yc + ip.c), dI = float(ip.a);
@@ -441,7 +576,7 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
             // op first (I = I0 + dI * k, clamped to [0, 4096]), then the
             // lookups and stores
             constexpr int kChunk = 64;
-            alignas(16) int i0[kChunk], i1[kChunk], i2[kChunk];
+            alignas(32) int i0[kChunk], i1[kChunk], i2[kChunk];
             const __m128 vI0 = _mm_set1_ps(I0), vdI = _mm_set1_ps(dI), lo = _mm_setzero_ps();
             const __m128 hi = _mm_set1_ps(4096.f), va0 = _mm_set1_ps(a0), va1 = _mm_set1_ps(a1);
             const __m128 va2 = _mm_set1_ps(a2), four = _mm_set1_ps(4.f);
@@ -449,7 +584,11 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
               const int n = std::min(kChunk, x1 - xb + 1);
               const float kb = float(xb - x0);
               __m128 kv = _mm_add_ps(_mm_set1_ps(kb), _mm_setr_ps(0.f, 1.f, 2.f, 3.f));
-              for (int k = 0; k < n; k += 4, kv = _mm_add_ps(kv, four)) {
+              if (avx2) {   // the same indices, 8 per op
+                tone_indices_avx2(i0, n, I0, dI, kb, a0);
+                if (!gray) tone_indices_avx2(i1, n, I0, dI, kb, a1), tone_indices_avx2(i2, n, I0, dI, kb, a2);
+              }
+              for (int k = 0; !avx2 && k < n; k += 4, kv = _mm_add_ps(kv, four)) {
                 const __m128 I = _mm_add_ps(vI0, _mm_mul_ps(vdI, kv));
                 _mm_store_si128(reinterpret_cast<__m128i*>(i0 + k),
                                 _mm_cvttps_epi32(_mm_min_ps(_mm_max_ps(_mm_mul_ps(va0, I), lo), hi)));
@@ -470,7 +609,8 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
                   else p[0] = T.v[i0[k]], p[1] = T.v[i1[k]], p[2] = T.v[i2[k]];
                 }
               } else if (C == 4 && gray) {
-                for (int k = 0; k < n; ++k) std::memcpy(p + size_t(k) * 4, &T.gray4[i0[k]], 4);
+                for (int k = avx2 ? store_gray4_avx2(p, i0, n, T.gray4) : 0; k < n; ++k)
+                  std::memcpy(p + size_t(k) * 4, &T.gray4[i0[k]], 4);
               } else if (C == 4) {
                 for (int k = 0; k < n; ++k) {
                   const uint32_t v = uint32_t(T.v[i0[k]]) | uint32_t(T.v[i1[k]]) << 8 |
@@ -480,7 +620,10 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
               } else if (gray) {
                 // packed RGB, as the shadow spans: 32-bit stores whose 4th
                 // byte the next pixel rewrites, the chunk's last pixel as 3 bytes
-                for (int k = 0; k + 1 < n; ++k, p += 3) std::memcpy(p, &T.gray4[i0[k]], 4);
+                // (AVX2: whole groups of 8 first, as 24 exact bytes each)
+                int k = avx2 ? store_gray3_avx2(p, i0, n, T.gray4) : 0;
+                if (k == n) continue;
+                for (p += size_t(k) * 3; k + 1 < n; ++k, p += 3) std::memcpy(p, &T.gray4[i0[k]], 4);
                 p[0] = p[1] = p[2] = T.v[i0[n - 1]];
               } else {
                 for (int k = 0; k < n; ++k, p += C) p[0] = T.v[i0[k]], p[1] = T.v[i1[k]], p[2] = T.v[i2[k]];
@@ -490,6 +633,23 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
         }
       }
     }
+  }
+  // restore after draw: what the previous frame wrote and this one did not
+  // cover goes back to the background -- the old span minus the row's
+  // intervals, taken in order of their left ends
+  for (int y = old_y0; y <= old_y1; ++y) {
+    const int n = cover_n_[size_t(y)];
+    const int a = prev_lo_[size_t(y)], b = prev_hi_[size_t(y)];
+    if (n == kRowRestored || a > b) continue;
+    int* c = &cover_[size_t(y) * kMaxCover * 2];
+    for (int i = 1; i < n; ++i)   // insertion sort of <= 7 intervals
+      for (int j = i; j > 0 && c[2 * j] < c[2 * j - 2]; --j) std::swap(c[2 * j], c[2 * j - 2]), std::swap(c[2 * j + 1], c[2 * j - 1]);
+    int cur = a;
+    for (int i = 0; i < n && cur <= b; ++i) {
+      if (c[2 * i] > cur) restore(y, cur, std::min(c[2 * i] - 1, b));
+      cur = std::max(cur, c[2 * i + 1] + 1);
+    }
+    if (cur <= b) restore(y, cur, b);
   }
   if (dirty) {
     touched.known = true;

@@ -153,9 +153,28 @@ class Renderer {
   std::vector<int> plane_x0_, plane_x1_;
   std::vector<uint8_t> plane_dense_;
   uint8_t shadow_rgb_[3];
+  uint8_t shadow_pat3_[96];              // 32 packed-RGB shadow pixels (vector fills)
   std::vector<float> depth_;             // 1/depth per pixel, zero outside depth_rect_
   DirtyRect depth_rect_;                // pixels of depth_ the last frame wrote
+  // Restore after draw (one box, buffer of known content): the frame is drawn
+  // first and records, per image row, the intervals it wrote in full (the
+  // shadow's interval on plane_dense_ rows, every face span); the previous
+  // frame's span is then restored minus those.  The cube turns in place under
+  // a fixed light, so most of the old span is overwritten anyway and never
+  // copied from the background first.
+  static constexpr int kMaxCover = 8;    // 1 shadow + 3 front faces x 2 triangles, and one spare
+  static constexpr uint8_t kRowRestored = 0xff;   // cover_n_: the row took the old order (restored before its draw)
+  std::vector<int> cover_;               // per row kMaxCover x [x0, x1]
+  std::vector<uint8_t> cover_n_;         // per row: intervals recorded, or kRowRestored
+  std::vector<int> prev_lo_, prev_hi_;   // the previous frame's row spans while this frame draws
 };
+
+// Which fill bodies render() uses: "avx2" (8 tone-table indices per op, a
+// gather and a byte shuffle per 8 pixels, 32-byte pattern stores for the
+// shadow) where the CPU has it, else "scalar" (the 4-wide SSE index code with
+// one store per pixel).  BLENDTORCH_RASTER_ISA=scalar|avx2 picks one; it is
+// read once.  Both write the same bytes.
+const char* raster_isa();
 
 // Triangle-mesh rendering (z-buffered, two-sided Lambert from a directional
 // light + ambient) over a uniform background -- used for parametric shapes

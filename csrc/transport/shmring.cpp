@@ -7,6 +7,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <thread>
@@ -17,6 +18,18 @@ namespace shm {
 namespace {
 std::string shm_path(const std::string& name) { return name[0] == '/' ? name : "/" + name; }
 size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// acquire() order (BLENDTORCH_SHM_SLOT_ORDER=lowest|rotate, read once):
+// "lowest" (default) takes the lowest free slot, so a producer whose consumer
+// keeps up writes into the few slots in flight and they stay in its caches;
+// "rotate" continues behind the slot taken last and walks the whole ring
+// (44 MB for 48 slots of 640x480 RGBA) whatever the consumer does.
+bool lowest_free_first() {
+  static const bool on = [] {
+    const char* e = std::getenv("BLENDTORCH_SHM_SLOT_ORDER");
+    return !(e && std::strcmp(e, "rotate") == 0);
+  }();
+  return on;
+}
 }  // namespace
 
 std::atomic<uint32_t>* Segment::states() const {
@@ -115,8 +128,9 @@ int Segment::acquire(long timeout_ms, const std::atomic<bool>* stop, long lease_
   if (published_at_.size() != n) published_at_.assign(n, 0);
   int spins = 0;
   for (;;) {
+    const uint32_t first = lowest_free_first() ? 0 : next_;
     for (uint32_t k = 0; k < n; ++k) {
-      const uint32_t i = (next_ + k) % n;
+      const uint32_t i = (first + k) % n;
       const uint32_t w = states()[i].load(std::memory_order_acquire);
       if ((w & 3u) == FREE) {
         states()[i].store((w & ~3u) | WRITING, std::memory_order_relaxed);

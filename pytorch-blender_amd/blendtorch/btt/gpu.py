@@ -330,8 +330,8 @@ class DeviceLoader:
         bytes they moved host -> device, over the time since the first frame;
         ``frames_per_producer``: frames per producer ``btid`` (provenance, as
         the reference's messages carry it); ``gpu_us_per_image``: device time
-        (H2D copies + decode kernel) per image, sampled every 16th launch with
-        timing events; ``images_per_launch``: launch coalescing;
+        (H2D copies + decode kernel) per image, sampled with timing events on
+        one launch per ~96 images; ``images_per_launch``: launch coalescing;
         ``consumer_wait_s``: time the consumer spent blocked on the next batch.
         """
         s = self._live.stats() if self._live is not None else dict(self.stats)
