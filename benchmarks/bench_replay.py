@@ -3,11 +3,16 @@
 batches gathered + decoded by one fused kernel per batch.
 
     python benchmarks/bench_replay.py [--frames 4096] [--batch 8] [--steps 2000] [--fill producers|synthetic]
+                                      [--crop H W] [--pad P] [--mirror p]
 
 ``--fill producers`` streams the frames from headless Cube producers through
 a raw-u8 DeviceLoader (the record-once, train-many-epochs workflow);
 ``synthetic`` writes random frames (same shape) straight into the store.
-Prints one JSON line (images/s of decoded fp32 CHW batches).
+``--crop H W`` samples through random windows (``--mirror p``: mirrored with
+probability p; ``--pad P``: replicate padding, ``--crop 480 640 --pad 4`` is
+the random shift of DrQ / RAD) inside the same launch.
+Prints one JSON line (images/s of decoded fp32 CHW batches); ``effective_tbps``
+counts the bytes read (the window's) plus the bytes written.
 """
 import argparse
 import json
@@ -31,7 +36,15 @@ def main():
     ap.add_argument('--sampler', choices=['fused', 'legacy'], default='fused',
                     help='fused: ONE launch (Philox draw + gather + decode + metadata); legacy: randint, '
                          'decode_gather and one index_select per metadata key (the round-1 path)')
+    ap.add_argument('--crop', type=int, nargs=2, metavar=('H', 'W'), default=None,
+                    help='sample through random H x W windows (fused sampler only)')
+    ap.add_argument('--pad', type=int, default=0, help='replicate padding of the crop (random shift)')
+    ap.add_argument('--mirror', type=float, default=0.0, help='probability of a mirrored window')
     a = ap.parse_args()
+    if a.crop is None and (a.pad or a.mirror):
+        ap.error('--pad and --mirror need --crop')
+    if a.crop is not None and a.sampler != 'fused':
+        ap.error('--crop needs the fused sampler')
 
     import torch
     from blendtorch import btt, ops
@@ -54,7 +67,8 @@ def main():
             rb.fill_from(dl, a.frames)
     torch.cuda.synchronize()
     fill_s = time.perf_counter() - t0
-    cfg = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, dtype=a.dtype)
+    crop = None if a.crop is None else ops.Crop(tuple(a.crop), mirror=a.mirror, pad=a.pad)
+    cfg = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, dtype=a.dtype, crop=crop)
     def legacy():
         idx = torch.randint(0, len(rb), (a.batch,), device=dev)
         out = {'image': ops.decode_gather(rb.store, idx, cfg), 'index': idx}
@@ -74,13 +88,17 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     H, W, C = rb.frame_shape
+    if crop is not None:   # the window's bytes: pixels outside the frame re-read an edge pixel
+        H, W = crop.size
     moved = a.batch * H * W * (C + cfg.cout * (4 if a.dtype == 'float32' else 2))   # bytes read + written
     print(json.dumps({'metric': 'replay images/s (HBM store -> gather+decode)', 'value': round(a.steps * a.batch / dt, 1),
                       'sampler': a.sampler, 'us_per_batch': round(dt / a.steps * 1e6, 2),
                       'effective_tbps': round(moved * a.steps / dt / 1e12, 3),
                       'unit': 'images/s', 'batch': a.batch, 'frames': a.frames, 'store_gb': round(rb.nbytes / 1e9, 2),
                       'fill': a.fill, 'fill_s': round(fill_s, 2), 'ms_per_batch': round(dt / a.steps * 1e3, 4),
-                      'dtype': a.dtype, 'graph': a.graph, 'out_shape': list(b['image'].shape)}), flush=True)
+                      'dtype': a.dtype, 'graph': a.graph, 'out_shape': list(b['image'].shape),
+                      'crop': None if crop is None else {'size': list(crop.size), 'pad': crop.pad,
+                                                         'mirror': crop.mirror}}), flush=True)
 
 
 if __name__ == '__main__':

@@ -177,6 +177,49 @@ struct ReplayParams {
 };
 hipError_t replay_sample(const DecodeParams& p, const ReplayParams& r, hipStream_t stream);
 
+// replay_sample() through a window of every sampled frame, optionally
+// mirrored, optionally leaving the frame by up to `pad` pixels (replicate
+// padding: the random shift of DrQ / RAD is the full-size window with a pad).
+// With full[b] what replay_sample() delivers for image b (upright after
+// flip_all) and (y0, x0, m) the image's window, origin in FRAME coordinates
+// (-pad <= y0 <= H + pad - h, -pad <= x0 <= W + pad - w):
+//   out[b, c, i, j] = full[b, c, clamp(y0 + i, 0, H - 1), clamp(x0 + (m ? w - 1 - j : j), 0, W - 1)]
+// The output image is Cout * h * w elements (dense, p.dst); p.H, p.W stay the
+// frame size.  Values are bit-identical to replay_sample()'s; only the
+// window's bytes are read.  The windows are, in this order of precedence:
+//   * windows_in: device int32 [B * 3] of (y0, x0, m) -- validated by the
+//     caller on the host; the kernel clamps the origin into the legal range,
+//     so whatever it holds no byte outside the frame is read;
+//   * mode kCropFixed: (y0, x0) for every image, never mirrored (pad == 0);
+//   * mode kCropRandom: drawn per image from a second Philox4x32-10 block, key
+//     window_key, counter words (b, C, C >> 32, 1) with C the launch's counter
+//     (the index draw keeps counter word 3 = 0: the indices do not depend on
+//     the crop).  With (o0, o1, o2) the block's first output words:
+//       y0 = -pad + ((o0 * (H + 2 pad - h + 1)) >> 32)
+//       x0 = -pad + ((o1 * ((W + 2 pad - w) / x_align + 1)) >> 32) * x_align
+//       m  = (o2 >> 8) < mirror_threshold          (probability * 2^24)
+//     The counter is read even when the indices are given (index_in); a
+//     device counter then advances by B as well.
+// crop_out (nullable) receives the int32 (y0, x0, m) of every image.
+// Limits: H + 2 pad, W + 2 pad <= 32767, h <= H + 2 pad, w <= W + 2 pad;
+// pad != 0 needs x_align == 1 and drawn or given windows; no colour kernel,
+// no per-image sources or destinations.  Anything else is
+// hipErrorInvalidValue, checked on the host: nothing is launched.
+enum { kCropRandom = 0, kCropFixed = 1 };
+struct ReplayCropParams {
+  int h = 0, w = 0, pad = 0;
+  int mode = kCropRandom;
+  int y0 = 0, x0 = 0;               // kCropFixed
+  int x_align = 1;
+  uint32_t mirror_threshold = 0;    // of 2^24
+  uint64_t window_key = 0;
+  const int32_t* windows_in = nullptr;
+  int32_t* crop_out = nullptr;
+  uint32_t ny = 0, nx = 0;          // set by replay_sample_crop: origins to draw from
+};
+hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                              hipStream_t stream);
+
 // Per-pixel affine colour transform on the MFMA units:
 //   out[b, c, y, x] = sum_k M[c][k] * lut[k][in[b, y, x, k]] + bias[c]
 // for RGBA u8 HWC input (Cin = 4), f32 NCHW output with Cout <= 4 channels;

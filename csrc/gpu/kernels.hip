@@ -1253,6 +1253,315 @@ hipError_t replay_sample(const DecodeParams& p, const ReplayParams& r, hipStream
 }
 
 // ---------------------------------------------------------------------------
+// fused replay sample through crop windows (kernels.h: replay_sample_crop)
+// ---------------------------------------------------------------------------
+// replay_vec_kernel's prologue, value path, stores and metadata units with
+// decode_crop_kernel's addressing: a lane owns PPT consecutive pixels of one
+// WINDOW row.  The windows are drawn (or read) in the block prologue next to
+// the frame indices and sit packed in LDS.  With a pad the window may leave
+// the frame: the row is clamped (whole groups), and a group whose PPT source
+// columns do not all lie in [0, W) reads its pixels one by one at the clamped
+// columns -- only bytes of its own pixels, no over-read; every other group
+// takes load_window_pixels and keeps its proof.
+namespace {
+
+// Philox4x32-10 with counter word 3 = c3: the four output words in the order
+// philox_word leaves its state (philox_word is word 0 of the block c3 = 0)
+__device__ __forceinline__ void philox_block(uint64_t key, uint64_t ctr, uint32_t b, uint32_t c3, uint32_t (&o)[4]) {
+  uint32_t c0 = b, c1 = uint32_t(ctr), c2 = uint32_t(ctr >> 32);
+  uint32_t k0 = uint32_t(key), k1 = uint32_t(key >> 32);
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  o[0] = c0, o[1] = c1, o[2] = c2, o[3] = c3;
+}
+
+// frame index and window per image: 8 KiB for kMaxReplayB images.  A window
+// is packed as y0 + pad (15 bits), x0 + pad (15 bits), mirror (bit 31): both
+// origins lie in [0, 32767] by the launch's limits.
+struct ReplayCropShared {
+  uint32_t tab[kTabWords];
+  uint32_t idx[kMaxReplayB];
+  uint32_t win[kMaxReplayB];
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ int64_t replay_frame(const ReplayParams& r, uint64_t ctr, int b) {
+  return r.index_in ? r.index_in[b]
+                    : int64_t((uint64_t(philox_word(r.seed, ctr, uint32_t(b))) * uint64_t(r.count)) >> 32);
+}
+
+// image b's window, packed.  Given windows are clamped into the legal range
+// (the caller validated them; the clamp keeps every read inside the frame
+// whatever the tensor holds).
+__device__ __forceinline__ uint32_t replay_window(const DecodeParams& p, const ReplayCropParams& c, uint64_t ctr,
+                                                  int b) {
+  int y0, x0, m = 0;
+  if (c.windows_in) {
+    y0 = clampi(c.windows_in[3 * b], -c.pad, p.H + c.pad - c.h);
+    x0 = clampi(c.windows_in[3 * b + 1], -c.pad, p.W + c.pad - c.w);
+    m = c.windows_in[3 * b + 2] != 0;
+  } else if (c.mode == kCropFixed) {
+    y0 = c.y0, x0 = c.x0;
+  } else {
+    uint32_t o[4];
+    philox_block(c.window_key, ctr, uint32_t(b), 1u, o);
+    y0 = int(__umulhi(o[0], c.ny)) - c.pad;
+    x0 = int(__umulhi(o[1], c.nx)) * c.x_align - c.pad;
+    m = (o[2] >> 8) < c.mirror_threshold;
+  }
+  return uint32_t(y0 + c.pad) | (uint32_t(x0 + c.pad) << 15) | (uint32_t(m) << 31);
+}
+
+// fills sh.idx / sh.win (block 0 also index_out / crop_out); the caller syncs
+__device__ __forceinline__ void replay_crop_table(const DecodeParams& p, const ReplayParams& r,
+                                                  const ReplayCropParams& c, uint64_t ctr, ReplayCropShared& sh) {
+  for (int b = threadIdx.x; b < p.B; b += kBlock) {
+    const int64_t i = replay_frame(r, ctr, b);
+    const uint32_t win = replay_window(p, c, ctr, b);
+    sh.idx[b] = uint32_t(i);
+    sh.win[b] = win;
+    if (blockIdx.x == 0) {
+      if (r.index_out) r.index_out[b] = i;
+      if (c.crop_out) {
+        c.crop_out[3 * b] = int(win & 0x7FFFu) - c.pad;
+        c.crop_out[3 * b + 1] = int((win >> 15) & 0x7FFFu) - c.pad;
+        c.crop_out[3 * b + 2] = int(win >> 31);
+      }
+    }
+  }
+}
+
+// PPT pixels of one frame row at columns clamp(xs + k, 0, W - 1): one pixel at
+// a time (a dword per RGBA pixel -- rows of a 16-byte aligned frame are dword
+// multiples --, three bytes per RGB pixel), every index static once unrolled
+template <int PPT, int CIN>
+__device__ __forceinline__ void load_clamped_pixels(const uint8_t* row, int xs, int W, Pixels<PPT, CIN>& px) {
+  constexpr int NW = Pixels<PPT, CIN>::NW;
+  if constexpr (CIN == 4) {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) px.w[k] = reinterpret_cast<const uint32_t*>(row)[clampi(xs + k, 0, W - 1)];
+  } else {
+    static_assert(CIN == 3, "packed RGB");
+    uint32_t o[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) o[k] = 0;
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+      const uint8_t* s = row + clampi(xs + i, 0, W - 1) * 3;
+      const uint32_t v = uint32_t(s[0]) | (uint32_t(s[1]) << 8) | (uint32_t(s[2]) << 16);
+      const int k = (3 * i) >> 2, sh = (3 * i) & 3;
+      o[k] |= v << (8 * sh);
+      if (sh >= 2) o[k + 1 < NW ? k + 1 : k] |= v >> (8 * (4 - sh));
+    }
+#pragma unroll
+    for (int k = 0; k < NW; ++k) px.w[k] = o[k];
+  }
+}
+
+// The lane's PPT source pixels of window row i, window columns [j, j + PPT),
+// in SOURCE order (the caller reverses them when the window is mirrored).
+template <int PPT, int CIN>
+__device__ __forceinline__ bool load_crop_group(const DecodeParams& p, const ReplayParams& r,
+                                                const ReplayCropParams& c, int64_t frame, uint32_t win, int i, int j,
+                                                Pixels<PPT, CIN>& px) {
+  const int y0 = int(win & 0x7FFFu) - c.pad, x0 = int((win >> 15) & 0x7FFFu) - c.pad;
+  const bool mirror = (win >> 31) != 0;
+  const int y = clampi(y0 + i, 0, p.H - 1);
+  const int sy = p.flip_all ? p.H - 1 - y : y;
+  const int xs = x0 + (mirror ? c.w - PPT - j : j);
+  const uint8_t* row = p.src + frame * r.frame_bytes + int64_t(sy) * p.W * CIN;
+  if (xs >= 0 && xs + PPT <= p.W)
+    load_window_pixels<PPT, CIN>(row + xs * CIN, px);
+  else   // pad only: the group straddles (or lies beyond) a frame edge
+    load_clamped_pixels<PPT, CIN>(row, xs, p.W, px);
+  return mirror;
+}
+
+// The two choices replay_vec_kernel settled by measurement, measured again
+// here (profiles/r12/replay_crop.md, 640x480 RGBA -> fp32 NCHW):
+//   * no first-group load ahead of the table staging and the barrier: every
+//     lane would run both Philox blocks of its first image itself, and the
+//     variant was 1-7 % slower from a graph (batch 8, 448x448: 16.0 against
+//     15.3 us; batch 64: 50.3 against 48.0 us) and 4 % slower eagerly at
+//     batch 64 (43.3 against 41.7 us);
+//   * NT: non-temporal stores for fp32 NCHW table-mode output, as in the
+//     uncropped kernel: batch 64 of 448x448 41.7 us against 48.1 with plain
+//     stores (eager), batch 8 from a graph 15.3 against 16.3; from a graph at
+//     batch 64 plain stores were 2 % ahead (46.8 against 48.0).
+template <int PPT, int CIN, int OUTT, int LAYOUT, int TBL, bool NT = false>
+__global__ __launch_bounds__(kBlock) void replay_crop_vec_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
+                                                                 int64_t meta_units) {
+  __shared__ ReplayCropShared sh;
+  const int64_t hw = int64_t(c.h) * c.w;       // window = output image
+  const int64_t groups_per_img = hw / PPT;
+  const int64_t groups = groups_per_img * p.B;
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cm[k] = p.cmap[k];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  const bool small = groups + meta_units + stride < (int64_t(1) << 31);
+  // the windows need the counter even when the indices are given
+  const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
+  const Xf xf = stage_xf(p.lut, sh.tab, p.Cout);
+  replay_crop_table(p, r, c, ctr, sh);
+  __syncthreads();
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < groups + meta_units; g += stride) {
+    if (g >= groups) {
+      replay_meta(r, sh, p.B, g - groups);
+      continue;
+    }
+    Group gr;
+    int i, j;
+    split_group<PPT>(g, groups_per_img, c.w, small, gr.b, gr.q, i, j);
+    Pixels<PPT, CIN> px;
+    // the mirror bit is per image and a wave may straddle two images: a
+    // branch into a static body, as in decode_crop_kernel
+    if (load_crop_group<PPT, CIN>(p, r, c, int64_t(sh.idx[gr.b]), sh.win[gr.b], i, j, px)) reverse_pixels<PPT, CIN>(px);
+    emit<PPT, CIN, OUTT, LAYOUT, TBL, NT>(p, xf, cm, cout, hw, gr, px);
+  }
+}
+
+// any window size / alignment / channel count: one window pixel per lane
+template <int OUTT>
+__global__ __launch_bounds__(kBlock) void replay_crop_scalar_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
+                                                                    int64_t meta_units) {
+  __shared__ ReplayCropShared sh;
+  const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
+  const Xf xf = stage_xf(p.lut, sh.tab, p.Cout);
+  replay_crop_table(p, r, c, ctr, sh);
+  __syncthreads();
+  const int64_t hw = int64_t(c.h) * c.w;
+  const int64_t total = hw * p.B;
+  const int64_t ie = hw * p.Cout;
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total + meta_units; g += int64_t(gridDim.x) * kBlock) {
+    if (g >= total) {
+      replay_meta(r, sh, p.B, g - total);
+      continue;
+    }
+    const int b = int(g / hw);
+    const int64_t q = g - int64_t(b) * hw;
+    const int i = int(q / c.w), j = int(q - int64_t(i) * c.w);
+    const uint32_t win = sh.win[b];
+    const int y0 = int(win & 0x7FFFu) - c.pad, x0 = int((win >> 15) & 0x7FFFu) - c.pad;
+    const int y = clampi(y0 + i, 0, p.H - 1);
+    const int sy = p.flip_all ? p.H - 1 - y : y;
+    const int x = clampi(x0 + ((win >> 31) ? c.w - 1 - j : j), 0, p.W - 1);
+    const uint8_t* s = p.src + int64_t(sh.idx[b]) * r.frame_bytes + (int64_t(sy) * p.W + x) * p.Cin;
+    for (int k = 0; k < p.Cout; ++k) {
+      const float v = xf_value(xf, k, s[p.cmap[k]]);
+      const int64_t off = int64_t(b) * ie + (p.layout == NCHW ? int64_t(k) * hw + q : q * p.Cout + k);
+      if constexpr (OUTT == OUT_F32) reinterpret_cast<float*>(p.dst)[off] = v;
+      else if constexpr (OUTT == OUT_BF16) reinterpret_cast<uint16_t*>(p.dst)[off] = f2bf(v);
+      else if constexpr (OUTT == OUT_F16) reinterpret_cast<uint16_t*>(p.dst)[off] = f2h(v);
+      else reinterpret_cast<uint8_t*>(p.dst)[off] = uint8_t(v);
+    }
+  }
+}
+
+template <int PPT, int CIN, int OUTT, int LAYOUT>
+void launch_replay_crop_vec(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                            int64_t meta_units, int grid, hipStream_t s) {
+  if constexpr (OUTT == OUT_F32 && LAYOUT == NCHW) {
+    if (p.xf_table_only) {
+      // non-temporal stores where they were measured (the kernel's comment);
+      // BT_REPLAY_CROP_NT=0: plain stores
+      static const bool nt = !(std::getenv("BT_REPLAY_CROP_NT") && std::getenv("BT_REPLAY_CROP_NT")[0] == '0');
+      if (nt) replay_crop_vec_kernel<PPT, CIN, OUTT, LAYOUT, 1, true><<<grid, kBlock, 0, s>>>(p, r, c, meta_units);
+      else replay_crop_vec_kernel<PPT, CIN, OUTT, LAYOUT, 1><<<grid, kBlock, 0, s>>>(p, r, c, meta_units);
+      return;
+    }
+  }
+  if (p.xf_table_only) replay_crop_vec_kernel<PPT, CIN, OUTT, LAYOUT, 1><<<grid, kBlock, 0, s>>>(p, r, c, meta_units);
+  else replay_crop_vec_kernel<PPT, CIN, OUTT, LAYOUT, 0><<<grid, kBlock, 0, s>>>(p, r, c, meta_units);
+}
+
+template <int OUTT>
+hipError_t launch_replay_crop(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                              int64_t meta_units, hipStream_t s) {
+  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  // decode_crop's vector conditions on replay's dense store and output
+  const bool vec = (c.w % PPT) == 0 && (p.W % 4) == 0 && r.frame_bytes % 16 == 0 && (p.Cin == 3 || p.Cin == 4) &&
+                   (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0 &&
+                   (int64_t(c.h) * c.w * p.Cout * ELEM) % 16 == 0;
+  if (vec) {
+    const int grid = grid_for(int64_t(p.B) * c.h * c.w / PPT + meta_units, p.max_grid);
+    if (p.Cin == 4) {
+      if (p.layout == NCHW) launch_replay_crop_vec<PPT, 4, OUTT, NCHW>(p, r, c, meta_units, grid, s);
+      else launch_replay_crop_vec<PPT, 4, OUTT, NHWC>(p, r, c, meta_units, grid, s);
+    } else {
+      if (p.layout == NCHW) launch_replay_crop_vec<PPT, 3, OUTT, NCHW>(p, r, c, meta_units, grid, s);
+      else launch_replay_crop_vec<PPT, 3, OUTT, NHWC>(p, r, c, meta_units, grid, s);
+    }
+  } else {
+    replay_crop_scalar_kernel<OUTT><<<grid_for(int64_t(p.B) * c.h * c.w + meta_units, p.max_grid), kBlock, 0, s>>>(
+        p, r, c, meta_units);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c0,
+                              hipStream_t stream) {
+  // every condition is checked here, before anything is launched
+  if (p.B < 0 || p.B > kMaxReplayB || p.H <= 0 || p.W <= 0 || p.Cin < 1 || p.Cin > 4 || p.Cout < 1 || p.Cout > 4 ||
+      !p.src || !p.dst || !p.lut || p.nsrcs || p.ndsts || p.src_offsets || p.flip || r.nmeta < 0 ||
+      r.nmeta > kMaxMeta || r.frame_bytes != int64_t(p.H) * p.W * p.Cin)
+    return hipErrorInvalidValue;
+  if (p.layout != NCHW && p.layout != NHWC) return hipErrorInvalidValue;
+  ReplayCropParams c = c0;
+  if (c.h <= 0 || c.w <= 0 || c.pad < 0 || c.pad > 16383 || p.H + 2 * c.pad > 32767 || p.W + 2 * c.pad > 32767 ||
+      c.h > p.H + 2 * c.pad || c.w > p.W + 2 * c.pad)
+    return hipErrorInvalidValue;
+  if (c.x_align != 1 && c.x_align != 4 && c.x_align != 16) return hipErrorInvalidValue;
+  if (c.mode != kCropRandom && c.mode != kCropFixed) return hipErrorInvalidValue;
+  if (c.mirror_threshold > (1u << 24)) return hipErrorInvalidValue;
+  if (c.pad != 0 && (c.x_align != 1 || (c.mode != kCropRandom && !c.windows_in))) return hipErrorInvalidValue;
+  if (c.mode == kCropFixed && !c.windows_in &&
+      (c.y0 < 0 || c.x0 < 0 || c.y0 + c.h > p.H || c.x0 + c.w > p.W))
+    return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(c.windows_in) | reinterpret_cast<uintptr_t>(c.crop_out)) % 4) return hipErrorInvalidValue;
+  if (!r.index_in && (r.count < 1 || r.count > (int64_t(1) << 32))) return hipErrorInvalidValue;
+  for (int k = 0; k < p.Cout; ++k)
+    if (p.cmap[k] < 0 || p.cmap[k] >= p.Cin) return hipErrorInvalidValue;
+  int64_t meta_units = 0;
+  for (int k = 0; k < r.nmeta; ++k) {
+    const int nb = r.meta_bytes[k];
+    if (nb <= 0 || !r.meta_src[k] || !r.meta_dst[k]) return hipErrorInvalidValue;
+    if (nb % 4 == 0 && ((reinterpret_cast<uintptr_t>(r.meta_src[k]) | reinterpret_cast<uintptr_t>(r.meta_dst[k])) % 4))
+      return hipErrorInvalidValue;
+    meta_units += int64_t(p.B) * (nb % 4 == 0 ? nb / 4 : nb);
+  }
+  if (p.B == 0) return hipSuccess;
+  c.ny = uint32_t(p.H + 2 * c.pad - c.h + 1);
+  c.nx = uint32_t((p.W + 2 * c.pad - c.w) / c.x_align + 1);
+  hipError_t e = hipErrorInvalidValue;
+  switch (p.out_dtype) {
+    case OUT_F32: e = launch_replay_crop<OUT_F32>(p, r, c, meta_units, stream); break;
+    case OUT_BF16: e = launch_replay_crop<OUT_BF16>(p, r, c, meta_units, stream); break;
+    case OUT_F16: e = launch_replay_crop<OUT_F16>(p, r, c, meta_units, stream); break;
+    case OUT_U8: e = launch_replay_crop<OUT_U8>(p, r, c, meta_units, stream); break;
+  }
+  // a device counter moves on when this launch drew from it: indices, or windows
+  const bool drew = !r.index_in || (c.mode == kCropRandom && !c.windows_in);
+  if (e != hipSuccess || !r.counter || !drew) return e;
+  replay_advance_kernel<<<1, 1, 0, stream>>>(r.counter, p.B);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // color4x4 on MFMA (v_mfma_f32_4x4x1_16b_f32)
 // ---------------------------------------------------------------------------
 namespace {

@@ -362,7 +362,9 @@ PYBIND11_MODULE(_hip, m) {
         [](uintptr_t store, int64_t count, uintptr_t dst, uintptr_t lut, int B, int H, int W, int Cin, int Cout,
            std::vector<int> cmap, int flip_all, int out_dtype, int layout, uint64_t seed, uintptr_t counter,
            uint64_t ctr_value, uintptr_t index_in, uintptr_t index_out, std::vector<uintptr_t> meta_src, std::vector<uintptr_t> meta_dst,
-           std::vector<int> meta_bytes, uintptr_t stream, int xf_table_only, int max_grid) {
+           std::vector<int> meta_bytes, uintptr_t stream, int xf_table_only, int max_grid,
+           std::vector<int> crop_size, std::string crop_mode, std::vector<int> crop_origin, int crop_pad, double mirror,
+           int x_align, uint64_t window_key, uintptr_t windows_in, uintptr_t crop_out) {
           DecodeParams p;
           p.xf_table_only = xf_table_only;
           p.max_grid = max_grid;
@@ -391,13 +393,42 @@ PYBIND11_MODULE(_hip, m) {
             r.meta_dst[k] = ptr<uint8_t>(meta_dst[size_t(k)]);
             r.meta_bytes[k] = meta_bytes[size_t(k)];
           }
-          check(replay_sample(p, r, stream_of(stream)), "replay_sample");
+          if (crop_size.empty()) {
+            check(replay_sample(p, r, stream_of(stream)), "replay_sample");
+            return;
+          }
+          // through a window (crop_size = h, w) of every sampled frame (kernels.h: replay_sample_crop)
+          if (crop_size.size() != 2 || (!crop_origin.empty() && crop_origin.size() != 2))
+            throw std::invalid_argument("replay_sample: crop_size is (h, w) and crop_origin (y0, x0)");
+          if (!(mirror >= 0.0 && mirror <= 1.0)) throw std::invalid_argument("replay_sample: mirror is a probability");
+          ReplayCropParams c;
+          c.h = crop_size[0], c.w = crop_size[1], c.pad = crop_pad;
+          c.x_align = x_align;
+          if (!crop_origin.empty()) {
+            c.mode = kCropFixed, c.y0 = crop_origin[0], c.x0 = crop_origin[1];
+          } else if (crop_mode == "center") {
+            c.mode = kCropFixed;
+            c.y0 = (H - c.h) / 2;
+            c.x0 = x_align > 0 ? (W - c.w) / 2 / x_align * x_align : 0;
+          } else if (crop_mode == "random") {
+            c.mode = kCropRandom;
+          } else {
+            throw std::invalid_argument("replay_sample: crop_mode is 'random' or 'center'");
+          }
+          c.mirror_threshold = uint32_t(mirror * 16777216.0);
+          c.window_key = window_key;
+          c.windows_in = ptr<const int32_t>(windows_in);
+          c.crop_out = ptr<int32_t>(crop_out);
+          check(replay_sample_crop(p, r, c, stream_of(stream)), "replay_sample_crop");
         },
         py::arg("store"), py::arg("count"), py::arg("dst"), py::arg("lut"), py::arg("B"), py::arg("H"), py::arg("W"),
         py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"),
         py::arg("seed"), py::arg("counter"), py::arg("ctr_value"), py::arg("index_in"), py::arg("index_out"), py::arg("meta_src"),
         py::arg("meta_dst"), py::arg("meta_bytes"), py::arg("stream"), py::arg("xf_table_only") = 0,
-        py::arg("max_grid") = 0);
+        py::arg("max_grid") = 0, py::arg("crop_size") = std::vector<int>(), py::arg("crop_mode") = "random",
+        py::arg("crop_origin") = std::vector<int>(), py::arg("crop_pad") = 0, py::arg("mirror") = 0.0,
+        py::arg("x_align") = 1, py::arg("window_key") = uint64_t(0), py::arg("windows_in") = uintptr_t(0),
+        py::arg("crop_out") = uintptr_t(0));
 
   m.def("multi_cast",
         [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst, std::vector<int64_t> numel, int mode,

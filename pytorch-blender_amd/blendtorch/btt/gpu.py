@@ -187,6 +187,8 @@ class DeviceLoader:
             addresses = [addresses]
         self.addresses = list(addresses)
         self.batch_size = int(batch_size)
+        if decode.crop is not None:
+            decode.crop.no_pad('DeviceLoader')   # replicate padding exists on the replay path only
         self.decode = decode
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())

@@ -20,6 +20,11 @@ epoch after the first then runs at HBM speed without touching the host:
   (``ops.decode_gather``: the kernel reads frame ``index[b]`` straight from the
   store; the gathered u8 batch is never materialised). Per-item metadata
   (``btid``, ``frameid``, ``xy``, ...) is gathered on the device too.
+* ``DecodeConfig(crop=ops.Crop(...))``: the same launch also draws a window
+  per image (Philox, next to the index draw) and decodes through it: random
+  crop + mirror, or with ``Crop(frame_size, pad=4)`` the random shift of
+  DrQ / RAD (replicate padding).  The batch reports its windows as
+  ``batch['crop']``; a graphed sampler draws fresh ones on every replay.
 
 On a CPU device the same API runs with the fp32 reference ops (tests, hosts
 without a GPU). On a GPU device the HIP kernels are required and fail loudly
@@ -243,37 +248,94 @@ class DeviceReplayBuffer:
             return ops.decode(imgs, decode)
         return ops.reference_decode(imgs, decode)
 
-    def gather(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig()):
+    def _windows(self, B: int, crop, windows, ctr: int) -> np.ndarray:
+        """int32 [B, 3] windows of a sample on the reference path: the given ones (validated),
+        else what the fused kernel draws at Philox counter ``ctr`` (ops.replay_windows)."""
+        H, W = self.frame_shape[:2]
+        crop.check_frame(H, W)
+        if windows is None:
+            return ops.replay_windows(crop, H, W, B, seed=self.seed, counter=ctr)
+        win = windows.detach().cpu().numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if win.shape != (B, 3) or win.dtype.kind not in 'iu':
+            raise ValueError(f'windows must be integers [{B}, 3] (y0, x0, mirrored)')
+        ops._check_windows(win.astype(np.int64), crop, H, W)
+        return np.ascontiguousarray(win, dtype=np.int32)
+
+    def gather(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig(), windows=None, _counter=None):
         """Decoded frames ``idx`` (device int tensor) + their metadata.  On a
         GPU: one fused launch decodes the frames and gathers every metadata
-        column (``ops.replay_sample`` with given indices)."""
+        column (``ops.replay_sample`` with given indices).
+
+        With ``decode.crop`` the frames are decoded through windows inside
+        the same launch and the batch carries ``batch['crop']`` (int32 [B, 3]:
+        y0, x0, mirrored; ``ops.crop_points`` maps coordinates into them).  A
+        random crop draws its windows at the buffer's Philox counter, which
+        then advances by the batch size; ``windows`` ([B, 3], host values or a
+        tensor; eager use only) gives them instead."""
         if self._size == 0:
             raise IndexError('empty replay buffer')
         idx = idx.to(self.device, torch.int64)
-        if self._fused(decode):
-            img, idx, meta = ops.replay_sample(self.store, self._size, int(idx.numel()), decode, index=idx,
-                                               meta=self.meta)
-            return {self.image_key: img, **meta, 'index': idx}
-        out = {self.image_key: self._decode(idx, decode)}
+        crop = decode.crop
+        if crop is None:
+            if windows is not None:
+                raise ValueError('crop windows given for a config without a crop')
+            if self._fused(decode):
+                img, idx, meta = ops.replay_sample(self.store, self._size, int(idx.numel()), decode, index=idx,
+                                                   meta=self.meta)
+                return {self.image_key: img, **meta, 'index': idx}
+            out = {self.image_key: self._decode(idx, decode)}
+            for k, v in self.meta.items():
+                out[k] = v.index_select(0, idx)
+            out['index'] = idx
+            return out
+        B = int(idx.numel())
+        ctr = _counter
+        if ctr is None:
+            ctr = self._ctr
+            if crop.kind == 'random' and windows is None:   # the windows are drawn: the counter moves on
+                self._ctr += B
+        if self.device.type == 'cuda':
+            img, idx, meta, win = ops.replay_sample(self.store, self._size, B, decode, seed=self.seed, counter=ctr,
+                                                    index=idx, meta=self.meta, windows=windows)
+            return {self.image_key: img, **meta, 'index': idx, 'crop': win}
+        win = self._windows(B, crop, windows, ctr)
+        out = {self.image_key: ops.reference_decode(self.store.index_select(0, idx), decode, crop=win)}
         for k, v in self.meta.items():
             out[k] = v.index_select(0, idx)
         out['index'] = idx
+        out['crop'] = torch.from_numpy(win).to(self.device)
         return out
 
     def sample(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), generator=None, _counter=None):
         """Uniform random batch (with replacement).  On a GPU (no ``generator``)
         ONE fused launch draws the indices (Philox), decodes the frames and
         gathers their metadata; with a ``torch.Generator`` the indices come
-        from ``torch.randint`` instead."""
+        from ``torch.randint`` instead.
+
+        With ``decode.crop`` the same launch also draws the windows
+        (``batch['crop']``).  A CPU buffer then draws indices and windows with
+        the numpy references of the kernel's Philox draws
+        (``ops.philox_indices`` / ``ops.philox_windows``): a CPU buffer and a
+        GPU buffer with the same seed and call sequence return the same
+        batches.  With a ``generator`` only the indices come from it."""
         if self._size == 0:
             raise IndexError('empty replay buffer')
         if generator is None and self._fused(decode):
             ctr = _counter
             if ctr is None:
                 ctr, self._ctr = self._ctr, self._ctr + batch_size
+            if decode.crop is not None:
+                img, idx, meta, win = ops.replay_sample(self.store, self._size, batch_size, decode, seed=self.seed,
+                                                        counter=ctr, meta=self.meta)
+                return {self.image_key: img, **meta, 'index': idx, 'crop': win}
             img, idx, meta = ops.replay_sample(self.store, self._size, batch_size, decode, seed=self.seed,
                                                counter=ctr, meta=self.meta)
             return {self.image_key: img, **meta, 'index': idx}
+        if decode.crop is not None and generator is None and self.device.type != 'cuda':
+            # the fused sample on the reference path: one counter for indices and windows
+            ctr, self._ctr = self._ctr, self._ctr + batch_size
+            idx = torch.from_numpy(ops.philox_indices(self.seed, ctr, batch_size, self._size))
+            return self.gather(idx, decode, _counter=ctr)
         idx = torch.randint(0, self._size, (batch_size,), device=self.device, generator=generator)
         return self.gather(idx, decode)
 

@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 __all__ = [
-    'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
+    'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'philox_windows', 'replay_windows', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
     'color4x4',
     'project', 'adaptive_avg_pool_nhwc', 'AdaptiveAvgPool2d', 'batch_norm_leaky_relu', 'BatchNormLeakyReLU2d',
     'reference_decode', 'reference_color4x4', 'reference_project', 'reference_gamma',
@@ -167,6 +167,18 @@ class Crop:
         (source addresses of RGBA frames then share that many pixels'
         alignment).
 
+    pad: replicate padding, on the replay path only
+        (:func:`replay_sample`, ``DeviceReplayBuffer``): the window may leave
+        the frame by up to ``pad`` pixels on every side, its origin lies in
+        ``[-pad, H + pad - h] x [-pad, W + pad - w]`` (frame coordinates) and
+        pixels outside the frame repeat the nearest edge pixel::
+
+            out[b, c, i, j] = full[b, c, clamp(y0 + i, 0, H - 1), clamp(x0 + (w - 1 - j if m else j), 0, W - 1)]
+
+        The full-size window with ``pad=4`` is the random shift of DrQ / RAD.
+        Needs ``x_align == 1`` and ``mode='random'`` (or given windows); the
+        stream loader, :func:`decode` and :func:`crop_windows` reject it.
+
     The stream loader reports each batch's windows as ``batch['crop']``
     (int32 [B, 3]: y0, x0, mirrored) and does not touch the metadata:
     :func:`crop_points` maps pixel coordinates into the window.  The
@@ -178,6 +190,7 @@ class Crop:
     mirror: float = 0.0
     seed: int = 0
     x_align: int = 1
+    pad: int = 0
 
     def __post_init__(self):
         try:
@@ -202,16 +215,33 @@ class Crop:
         if self.x_align not in (1, 4, 16):
             raise ValueError('Crop.x_align must be 1, 4 or 16')
         object.__setattr__(self, 'seed', int(self.seed))
+        if isinstance(self.pad, bool) or int(self.pad) != self.pad or not 0 <= int(self.pad) <= 16383:
+            raise ValueError('Crop.pad must be an integer >= 0 (frame + 2 * pad <= 32767)')
+        object.__setattr__(self, 'pad', int(self.pad))
+        if self.pad:
+            if self.x_align != 1:
+                raise ValueError('Crop.pad needs x_align == 1')
+            if self.kind != 'random':
+                raise ValueError("Crop.pad needs mode 'random' and no fixed origin")
 
     @property
     def kind(self):
         """'fixed' with an origin, else the mode."""
         return 'fixed' if self.origin is not None else self.mode
 
+    def no_pad(self, where):
+        """ValueError for a padded crop on a path that has no padding (the stream side)."""
+        if self.pad:
+            raise ValueError(f'{where}: Crop.pad is honoured by the replay path only '
+                             '(ops.replay_sample, DeviceReplayBuffer)')
+
     def check_frame(self, H, W):
-        """ValueError unless the window lies inside an H x W frame."""
+        """ValueError unless the window lies inside an H x W frame (padded by ``pad`` on every side)."""
         h, w = self.size
         y0, x0 = self.origin if self.origin is not None else (0, 0)
+        if self.pad and (H + 2 * self.pad > 32767 or W + 2 * self.pad > 32767):
+            raise ValueError(f'a {H}x{W} frame padded by {self.pad} exceeds 32767 pixels')
+        H, W = H + 2 * self.pad, W + 2 * self.pad
         if y0 + h > H or x0 + w > W:
             at = f' at {self.origin}' if self.origin is not None else ''
             raise ValueError(f'a {h}x{w} crop window{at} does not fit a {H}x{W} frame')
@@ -225,6 +255,7 @@ def crop_windows(crop: Crop, H: int, W: int, n: int) -> np.ndarray:
     ``y0 = ((z >> 32) * (H - h + 1)) >> 32``,
     ``x0 = (((z >> 32) * ((W - w) // x_align + 1)) >> 32) * x_align``,
     ``m = (z >> 40) < int(mirror * 2**24)``."""
+    crop.no_pad('crop_windows')
     crop.check_frame(H, W)
     h, w = crop.size
     out = np.zeros((n, 3), np.int32)
@@ -612,6 +643,17 @@ def reference_decode(images, cfg: DecodeConfig, flip=None, jitter=None, crop=Non
         ya, xa = (2, 3) if cfg.layout == 'nchw' else (1, 2)
         cfg.crop.check_frame(full.shape[ya], full.shape[xa])
         outs = []
+        if cfg.crop.pad:
+            # replicate padding: index with clamped coordinates (origin in frame coordinates)
+            H, W, pad = full.shape[ya], full.shape[xa], cfg.crop.pad
+            for b, (y0, x0, m) in enumerate(_crop_rows(crop, full.shape[0])):
+                if y0 < -pad or x0 < -pad or y0 + h > H + pad or x0 + w > W + pad:
+                    raise ValueError(f'crop window {(y0, x0)} + {(h, w)} leaves the frame padded by {pad}')
+                cols = torch.arange(w - 1, -1, -1) if m else torch.arange(w)
+                ys = (y0 + torch.arange(h)).clamp(0, H - 1).to(full.device)
+                xs = (x0 + cols).clamp(0, W - 1).to(full.device)
+                outs.append(full[b].index_select(ya - 1, ys).index_select(xa - 1, xs))
+            return torch.stack(outs)
         for b, (y0, x0, m) in enumerate(_crop_rows(crop, full.shape[0])):
             if y0 < 0 or x0 < 0 or y0 + h > full.shape[ya] or x0 + w > full.shape[xa]:
                 raise ValueError(f'crop window {(y0, x0)} + {(h, w)} leaves the frame')
@@ -739,6 +781,8 @@ def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None, crop
     For a ``crop`` config, ``crop`` holds the [B, 3] windows (y0, x0,
     mirrored) of the batch, e.g. from :func:`crop_windows` (B <= 64)."""
     import torch
+    if cfg.crop is not None:
+        cfg.crop.no_pad('decode')
     ext = hip_ext()
     if images.dtype != torch.uint8 or not images.is_cuda:
         raise TypeError('decode expects a uint8 CUDA/HIP tensor')
@@ -813,24 +857,81 @@ def philox_indices(seed: int, counter: int, B: int, count: int) -> np.ndarray:
     """The frame indices :func:`replay_sample` draws (numpy reference):
     Philox4x32-10 with key ``seed`` and counter ``(b, counter)`` for image b,
     first output word scaled to ``[0, count)`` as ``(word * count) >> 32``."""
+    c0 = _philox_blocks(seed, counter, B, 0)[0]
+    return ((c0 * np.uint64(count)) >> np.uint64(32)).astype(np.int64)
+
+
+def _philox_blocks(key: int, counter: int, B: int, word3: int):
+    """Philox4x32-10 blocks of the counters ``(b, counter & 0xffffffff,
+    counter >> 32, word3)``, b < B: the four output words as uint64 arrays."""
     M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
     mask = np.uint64(0xFFFFFFFF)
     c0 = np.arange(B, dtype=np.uint64)
     c1 = np.full(B, counter & 0xFFFFFFFF, np.uint64)
     c2 = np.full(B, (counter >> 32) & 0xFFFFFFFF, np.uint64)
-    c3 = np.zeros(B, np.uint64)
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    c3 = np.full(B, word3 & 0xFFFFFFFF, np.uint64)
+    k0, k1 = key & 0xFFFFFFFF, (key >> 32) & 0xFFFFFFFF
     for _ in range(10):
         p0, p1 = M0 * c0, M1 * c2          # < 2^64: exact in uint64
         hi0, lo0 = p0 >> np.uint64(32), p0 & mask
         hi1, lo1 = p1 >> np.uint64(32), p1 & mask
         c0, c1, c2, c3 = (hi1 ^ c1 ^ np.uint64(k0)), lo1, (hi0 ^ c3 ^ np.uint64(k1)), lo0
         k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    return ((c0 * np.uint64(count)) >> np.uint64(32)).astype(np.int64)
+    return c0, c1, c2, c3
+
+
+def replay_windows(crop: Crop, H: int, W: int, B: int, seed: int = 0, counter: int = 0) -> np.ndarray:
+    """int32 [B, 3]: the windows (y0, x0, mirrored) the replay path gives the
+    B images of one sample of H x W frames.  ``'center'`` and ``origin=``:
+    the window :func:`crop_windows` gives, for every image; ``'random'``:
+    :func:`philox_windows` at the sample's ``seed`` and ``counter``."""
+    if crop.kind == 'random':
+        return philox_windows(seed, counter, B, crop, H, W)
+    return crop_windows(crop, H, W, B)
+
+
+def philox_windows(seed: int, counter: int, B: int, crop: Crop, H: int, W: int) -> np.ndarray:
+    """The windows :func:`replay_sample` draws for a random ``crop`` (numpy
+    reference), int32 [B, 3] of (y0, x0, mirrored), origin in frame
+    coordinates (negative, or leaving the frame, with a ``pad``).  Image b
+    takes a second Philox4x32-10 block next to its index draw: key
+    ``(seed + crop.seed) mod 2**64``, counter words ``(b, counter &
+    0xffffffff, counter >> 32, 1)`` (:func:`philox_indices` has 0 in the last
+    word and the key ``seed``, so the indices do not depend on the crop).
+    With ``(o0, o1, o2)`` the block's first output words::
+
+        y0 = -pad + ((o0 * (H + 2*pad - h + 1)) >> 32)
+        x0 = -pad + ((o1 * ((W + 2*pad - w) // x_align + 1)) >> 32) * x_align
+        m  = (o2 >> 8) < int(mirror * 2**24)"""
+    if crop.kind != 'random':
+        raise ValueError("philox_windows: only mode 'random' draws its windows")
+    crop.check_frame(H, W)
+    h, w = crop.size
+    pad, a = crop.pad, crop.x_align
+    key = (int(seed) + crop.seed) & (2 ** 64 - 1)
+    o0, o1, o2, _ = _philox_blocks(key, int(counter) & (2 ** 64 - 1), B, 1)
+    out = np.zeros((B, 3), np.int32)
+    s32 = np.uint64(32)
+    out[:, 0] = ((o0 * np.uint64(H + 2 * pad - h + 1)) >> s32).astype(np.int64) - pad
+    out[:, 1] = ((o1 * np.uint64((W + 2 * pad - w) // a + 1)) >> s32).astype(np.int64) * a - pad
+    out[:, 2] = (o2 >> np.uint64(8)) < np.uint64(int(crop.mirror * 16777216.0))
+    return out
+
+
+def _check_windows(win, crop: Crop, H: int, W: int):
+    """ValueError unless every (y0, x0, m) of int [B, 3] ``win`` is a legal window of ``crop`` in H x W frames."""
+    h, w = crop.size
+    pad = crop.pad
+    ok = ((win[:, 0] >= -pad) & (win[:, 0] <= H + pad - h) & (win[:, 1] >= -pad) & (win[:, 1] <= W + pad - w)
+          & ((win[:, 2] == 0) | (win[:, 2] == 1)))
+    if not bool(np.all(ok)):
+        bad = [tuple(int(v) for v in r) for r in win[~ok][:3]]
+        raise ValueError(f'crop windows {bad} are not (y0, x0, mirrored) of a {h}x{w} window in a {H}x{W} frame'
+                         + (f' padded by {pad}' if pad else ''))
 
 
 def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfig(), seed: int = 0, counter=None,
-                  index=None, meta=None, out=None):
+                  index=None, meta=None, out=None, windows=None):
     """Fused replay sample on the gfx950 kernel: draw ``batch`` frame indices
     in ``[0, count)`` on the device (Philox, see :func:`philox_indices`) --
     or use ``index`` (int64 [batch]) -- decode those frames of ``store`` (u8
@@ -840,21 +941,51 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
     ``counter``: an int (the Philox counter; the caller advances it by
     ``batch``), or a device int64 tensor holding it -- then a one-lane kernel
     behind the sample advances it, so a captured HIP graph draws fresh
-    indices on every replay.  Returns ``(images, index, meta_out)``."""
+    indices on every replay.  Returns ``(images, index, meta_out)``.
+
+    With ``cfg.crop`` every frame is decoded through a window (and mirror, and
+    replicate ``pad``: :class:`Crop`) inside the same launch, and the call
+    returns ``(images, index, meta_out, crop)`` with ``crop`` the int32
+    [batch, 3] windows (y0, x0, mirrored).  A random crop draws them on the
+    device (:func:`philox_windows` with this ``seed`` and counter; also with a
+    given ``index``, which then needs the ``counter`` too); ``'center'`` and
+    ``origin=`` give every image the window of :func:`crop_windows`.
+    ``windows`` ([batch, 3], host values or a tensor) gives them instead: they
+    are validated on the host (``ValueError``, nothing is launched) and
+    uploaded -- eager use only, not inside a graph capture."""
     import torch
     ext = hip_ext()
     if store.dtype != torch.uint8 or not store.is_cuda or store.dim() != 4 or not store.is_contiguous():
         raise TypeError('replay_sample expects a contiguous uint8 [N,H,W,C] device tensor')
     if cfg.colour_kernel:
         raise ValueError('replay_sample does not apply colour matrices (use gather + color4x4)')
-    if cfg.crop is not None:
-        raise ValueError('replay_sample does not crop (use decode(store[index], cfg, crop=windows))')
     N, H, W, C = store.shape
     if max(cfg.cmap) >= C:
         raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
     dev = store.device
+    crop, ckw, crop_out, win_t = cfg.crop, {}, None, None
+    if crop is None and windows is not None:
+        raise ValueError('crop windows given for a config without a crop')
+    if crop is not None:
+        crop.check_frame(H, W)
+        if windows is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('replay_sample: given windows are uploaded from the host: not inside a graph capture')
+            win = windows.detach().cpu().numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+            if win.shape != (batch, 3) or win.dtype.kind not in 'iu':
+                raise ValueError(f'windows must be integers [{batch}, 3] (y0, x0, mirrored)')
+            _check_windows(win.astype(np.int64), crop, H, W)
+            win_t = torch.from_numpy(np.ascontiguousarray(win, dtype=np.int32)).to(dev)
+        crop_out = torch.empty((batch, 3), dtype=torch.int32, device=dev)
+        ckw = dict(crop_size=list(crop.size), crop_mode=crop.mode, crop_origin=list(crop.origin or ()),
+                   crop_pad=crop.pad, mirror=crop.mirror, x_align=crop.x_align,
+                   window_key=(int(seed) + crop.seed) & (2 ** 64 - 1),
+                   windows_in=0 if win_t is None else win_t.data_ptr(), crop_out=crop_out.data_ptr())
+    draws_windows = crop is not None and crop.kind == 'random' and windows is None
     if out is None:
         out = torch.empty(cfg.out_shape(batch, H, W), dtype=cfg.torch_dtype(), device=dev)
+    elif crop is not None and (tuple(out.shape) != tuple(cfg.out_shape(batch, H, W)) or not out.is_contiguous()):
+        raise ValueError('replay_sample: out must be a contiguous tensor of the window\'s shape')
     idx_out = torch.empty(batch, dtype=torch.int64, device=dev)
     idx_in, ctr_ptr, ctr_value = 0, 0, 0
     if index is not None:
@@ -862,6 +993,8 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
         if index.numel() != batch:
             raise ValueError('index needs one entry per image')
         idx_in = index.data_ptr()
+    if index is not None and not draws_windows:
+        counter = None          # nothing is drawn
     elif isinstance(counter, torch.Tensor):
         if counter.dtype != torch.int64 or counter.numel() < 1 or counter.device != dev:
             raise ValueError('a device counter must be an int64 tensor on the store\'s device')
@@ -869,7 +1002,7 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
     elif counter is not None:
         ctr_value = int(counter) & (2 ** 64 - 1)
     else:
-        raise ValueError('drawing indices needs a counter (int or device tensor)')
+        raise ValueError('drawing indices or windows needs a counter (int or device tensor)')
     meta = meta or {}
     mout, src, dst, nbytes = {}, [], [], []
     for k, col in meta.items():
@@ -884,7 +1017,9 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
     ext.replay_sample(store.data_ptr(), int(count), out.data_ptr(), lut.data_ptr(), batch, H, W, C, cfg.cout,
                       cfg.cmap, int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], int(seed) & (2 ** 64 - 1),
                       ctr_ptr, ctr_value, idx_in, idx_out.data_ptr(), src, dst, nbytes,
-                      _stream(dev), table_only(cfg, dev))
+                      _stream(dev), table_only(cfg, dev), **ckw)
+    if crop is not None:
+        return out, idx_out, mout, crop_out
     return out, idx_out, mout
 
 
