@@ -8,6 +8,10 @@ no consumer, the producer count bench.py plans) run with no crop and with
 every host frame, so a window moves ``h*w / (H*W)`` of the bytes over PCIe.
 
 Every run is a child process of its own (fresh producers, fresh HIP runtime);
+``resized224`` and ``resize224_full`` are ``ops.ResizedCrop((224, 224))`` rows: the
+default random window (``mirror=0.5``) and the whole frame resized; their
+``bytes_share`` is the windows' measured share of the frames, an upper bound of
+what is read once the vertical scale exceeds 2.
 the configurations alternate, ``--repeats`` rounds.  One JSON row per run on
 stdout: images/s over the timed steps, the loader's ``h2d_gbytes_per_s`` and
 ``gpu_us_per_image`` over the same window, ``direct_batches``, CPU us per frame.
@@ -31,6 +35,10 @@ CONFIGS = {
     'crop448': dict(size=(448, 448), mirror=0.5),
     'crop224': dict(size=(224, 224), mirror=0.5),
     'crop448_x16': dict(size=(448, 448), mirror=0.5, x_align=16),
+    # resized crops (ops.ResizedCrop: the frame's window resized inside the decode): the default random
+    # scale / ratio, and the whole frame (a plain Resize)
+    'resized224': dict(resize=True, size=(224, 224), mirror=0.5),
+    'resize224_full': dict(resize=True, size=(224, 224), mode='full'),
 }
 
 
@@ -72,8 +80,10 @@ def child(args):
         os.sched_setaffinity(0, rp['domain'])
     nprod, shm_slots = rp['producers'], rp['shm_slots']
     spec = CONFIGS[args.child]
-    crop = ops.Crop(**spec) if spec else None
-    decode = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, crop=crop)
+    resize = bool(spec) and spec.get('resize', False)
+    crop = None if resize or not spec else ops.Crop(**spec)
+    rc = ops.ResizedCrop(**{k: v for k, v in spec.items() if k != 'resize'}) if resize else None
+    decode = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, crop=crop, resize=rc)
     WARM_RESERVE = 2000
     total = args.warmup + args.steps + WARM_RESERVE
     with btt.BlenderLauncher(producer='cubesim', num_instances=nprod, named_sockets=['DATA'],
@@ -92,8 +102,11 @@ def child(args):
         torch.cuda.synchronize()
         cg0, ru0, snap0 = bench.cgroup_cpu_stat(), os.times(), dl.snapshot()
         t0 = time.perf_counter()
+        area = 0
         for _ in range(args.steps):
             b = next(it)
+            if rc is not None:   # the windows' share of the frames (host metadata: no device work)
+                area += int((b['window'][:, 2].long() * b['window'][:, 3].long()).sum())
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         snap1, ru1, cg1 = dl.snapshot(), os.times(), bench.cgroup_cpu_stat()
@@ -105,6 +118,7 @@ def child(args):
     if 'usage_usec' in cg0 and 'usage_usec' in cg1:
         cpu['total'] = round((cg1['usage_usec'] - cg0['usage_usec']) / frames, 2)
     hh, ww = crop.size if crop else (H, W)
+    share = area / (frames * H * W) if rc is not None else hh * ww / (H * W)
     print(json.dumps({
         'config': args.child, 'crop': spec, 'images_per_s': round(frames / elapsed, 1),
         'h2d_gbytes_per_s': round(win['h2d_gbytes_per_s'], 2),
@@ -112,7 +126,7 @@ def child(args):
         'direct_batches': snap1['direct_batches'] - snap0['direct_batches'], 'batches': args.steps,
         'planar_frames': snap1['planar_frames'] - snap0['planar_frames'],
         'images_per_launch': None if win['images_per_launch'] is None else round(win['images_per_launch'], 2),
-        'bytes_share': round(hh * ww / (H * W), 4), 'out_shape': shape, 'cpu_us_per_frame': cpu,
+        'bytes_share': round(share, 4), 'out_shape': shape, 'cpu_us_per_frame': cpu,
         'producers': nprod, 'hw_queues': hw_queues, 'steps': args.steps, 'warmup': n_warm,
         'backlog_covers_window': win.get('backlog_covers_window'), 'elapsed_s': round(elapsed, 4)}), flush=True)
     return 0

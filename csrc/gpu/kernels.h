@@ -106,6 +106,45 @@ struct CropParams {
 };
 hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t stream);
 
+// decode() of a window of every image, resized to oh x ow (bilinear, half-pixel
+// centres, no antialiasing: F.interpolate(mode='bilinear', align_corners=False)),
+// then optionally mirrored.  With full[b] what decode() delivers for image b
+// in fp32 (upright after its flip, table values before the output dtype) and
+// win = full[b][:, y0:y0+h, x0:x0+w], every fp32 operation rounded on its own
+// (no fma contraction).  Per axis, n_in the window and n_out the output extent:
+//   scale = float(n_in) / float(n_out)          (sy[b], sx[b]: set by the caller)
+//   s  = max((float(d) + 0.5f) * scale - 0.5f, 0.0f)
+//   i0 = min(int(floor(s)), n_in - 1);  i1 = min(i0 + 1, n_in - 1)
+//   l1 = s - float(i0);  l0 = 1.0f - l1
+// and, rows blended horizontally first:
+//   top = win[c, y_i0, x_i0] * lx0 + win[c, y_i0, x_i1] * lx1
+//   bot = win[c, y_i1, x_i0] * lx0 + win[c, y_i1, x_i1] * lx1
+//   r[c, i, j]   = top * ly0 + bot * ly1
+//   out[c, i, j] = r[c, i, m_b ? ow - 1 - j : j]
+// f32 as is; bf16 / f16 round r to nearest even; u8 is clamp(rint(r), 0, 255),
+// ties to even.  With h == oh and w == ow every l1 is 0 and the values are
+// decode_crop's.  p.H, p.W stay the SOURCE frame size; the output image is
+// Cout * oh * ow elements, dense or dsts[b].  p.B <= kMaxSrcs.
+// The frame is read in runs, never tap by tap (host frames are uncached over
+// the link): a block owns a band of R consecutive output rows of one image,
+// stages the window span [x0, x0 + w) of the source rows the band's taps
+// touch (at most 2R; rows between taps are not read once the vertical scale
+// exceeds 2) as raw bytes into LDS with aligned dword / 16-byte loads, and
+// after one barrier every lane produces its pixels from LDS only.  The
+// launcher lowers R for wide windows (<= 56 KiB of rows beside the 8-KiB value
+// table); a window row that does not fit twice is hipErrorInvalidValue, as is
+// a window outside the frame, h or w < 1, oh or ow < 1 and a bad channel map
+// -- all checked on the host: nothing is launched.  Cin 3 or 4 with 16-byte
+// aligned sources and destinations take the staged kernel (Cin == 3: W % 4 ==
+// 0 as well); anything else a one-pixel-per-thread kernel.  p.unroll is ignored.
+struct ResizeParams {
+  int oh = 0, ow = 0;
+  int16_t y0[kMaxSrcs] = {}, x0[kMaxSrcs] = {}, h[kMaxSrcs] = {}, w[kMaxSrcs] = {};
+  float sy[kMaxSrcs] = {}, sx[kMaxSrcs] = {};   // float(h) / float(oh), float(w) / float(ow)
+  uint64_t mirror_bits = 0;
+};
+hipError_t decode_resize(const DecodeParams& p, const ResizeParams& r, hipStream_t stream);
+
 // decode() of per-image sources (p.nsrcs == p.B <= kMaxSrcs, usually host
 // memory) of which only a region is read: image b's bytes in stored rows
 // [y0[b], y1[b]] x pixel columns [x0[b], x1[b]] (inclusive; y1 < y0: none)

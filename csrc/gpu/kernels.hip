@@ -876,6 +876,384 @@ hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t s
   return hipErrorInvalidValue;
 }
 
+// ---- resized crop (kernels.h: decode_resize) -------------------------------
+// The value path of decode() per tap, then a bilinear blend in which every
+// fp32 operation is rounded on its own.  A block owns a band of R output rows
+// of one image: it stages the window span of the source rows the band's taps
+// touch as raw bytes into LDS (the table is applied per tap: raw rows are
+// Cin bytes a pixel, so a 4096-pixel RGBA row fits twice; decoded fp32 rows of
+// Cout floats a pixel would not), and after one barrier every lane produces
+// PPT consecutive output pixels of one output row from LDS only.
+namespace {
+
+constexpr int kResizeRows = 56 * 1024;   // bytes of staged rows beside the 8-KiB value table: 64 KiB a block
+constexpr int kResizeBand = 8;           // output rows per band (lowered for wide windows)
+
+struct Axis {
+  int i0, i1;
+  float l0, l1;
+};
+
+// source taps and weights of output index d (kernels.h: decode_resize)
+__device__ __forceinline__ Axis resize_axis(int d, float scale, int n_in) {
+#pragma clang fp contract(off)
+  float s = (float(d) + 0.5f) * scale - 0.5f;
+  s = fmaxf(s, 0.0f);
+  Axis a;
+  a.i0 = min(int(s), n_in - 1);   // s >= 0: the conversion's truncation is floor
+  a.i1 = min(a.i0 + 1, n_in - 1);
+  a.l1 = s - float(a.i0);
+  a.l0 = 1.0f - a.l1;
+  return a;
+}
+
+__device__ __forceinline__ float resize_blend(float a, float b, float l0, float l1) {
+#pragma clang fp contract(off)
+  const float x = a * l0, y = b * l1;
+  return x + y;
+}
+
+// values of output channel c for N input bytes: lookup_static's value path
+template <int N>
+__device__ __forceinline__ void resize_values(const Xf& xf, int c, const uint32_t (&v)[N], float (&o)[N]) {
+  if (!xf.arith) {
+    const float* l = xf.lut + c * 256;
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = l[v[i]];
+    return;
+  }
+  float x[N];
+  if (xf.gam[c]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = float(xf.g[((v[i] >> 2) << xf.gshift) + (v[i] & 3)]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = float(v[i]);
+  }
+  const float a = xf.a[c], b = xf.b[c], d = xf.d[c], r = xf.r[c];
+  if (xf.op[c] == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = __builtin_fmaf(x[i], a, b);
+  } else if (xf.op[c] == 1) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = xf_mulsub(x[i], a, b);
+  } else if (xf.op[c] == 3) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = xf_recip_div(xf_mulsub(x[i], a, b), d, r);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = xf_mulsub(x[i], a, b) / d;
+  }
+}
+
+template <int OUTT>
+__device__ __forceinline__ auto resize_cvt(float v) {
+  if constexpr (OUTT == OUT_F32) return v;
+  else if constexpr (OUTT == OUT_BF16) return f2bf(v);
+  else if constexpr (OUTT == OUT_F16) return f2h(v);
+  else return uint8_t(fminf(fmaxf(__builtin_rintf(v), 0.0f), 255.0f));   // v_rndne: ties to even
+}
+
+// N values to N contiguous elements at the 16-byte aligned d (N * sizeof(element) a multiple of 16)
+template <int OUTT, int N>
+__device__ __forceinline__ void resize_store_run(void* d, const float (&v)[N]) {
+  if constexpr (OUTT == OUT_F32) {
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i)
+      reinterpret_cast<float4*>(d)[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+  } else if constexpr (OUTT == OUT_U8) {
+    uint32_t o[N / 4];   // packed in registers
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i)
+      o[i] = uint32_t(resize_cvt<OUTT>(v[4 * i])) | uint32_t(resize_cvt<OUTT>(v[4 * i + 1])) << 8 |
+             uint32_t(resize_cvt<OUTT>(v[4 * i + 2])) << 16 | uint32_t(resize_cvt<OUTT>(v[4 * i + 3])) << 24;
+#pragma unroll
+    for (int i = 0; i < N / 16; ++i)
+      reinterpret_cast<uint4*>(d)[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+  } else {
+    uint32_t o[N / 2];
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i)
+      o[i] = uint32_t(resize_cvt<OUTT>(v[2 * i])) | uint32_t(resize_cvt<OUTT>(v[2 * i + 1])) << 16;
+#pragma unroll
+    for (int i = 0; i < N / 8; ++i)
+      reinterpret_cast<uint4*>(d)[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+  }
+}
+
+// emit's stores for values already computed: v[c][u] of PPT pixels from pixel q of image b
+template <int PPT, int OUTT, int COUT>
+__device__ __forceinline__ void resize_store_nhwc(const DecodeParams& p, int b, int64_t hw, int64_t q,
+                                                  const float (&v)[4][PPT]) {
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  float o[PPT * COUT];
+#pragma unroll
+  for (int u = 0; u < PPT; ++u)
+#pragma unroll
+    for (int c = 0; c < COUT; ++c) o[u * COUT + c] = v[c][u];
+  resize_store_run<OUTT, PPT * COUT>(image_out<uint8_t>(p, b, hw * COUT * ELEM) + q * COUT * ELEM, o);
+}
+
+template <int PPT, int OUTT, int LAYOUT>
+__device__ __forceinline__ void resize_store(const DecodeParams& p, int b, int64_t hw, int cout, int64_t q,
+                                             const float (&v)[4][PPT]) {
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  if constexpr (LAYOUT == NCHW) {
+    uint8_t* img = image_out<uint8_t>(p, b, hw * cout * ELEM);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c >= cout) break;
+      resize_store_run<OUTT, PPT>(img + (int64_t(c) * hw + q) * ELEM, v[c]);
+    }
+  } else {
+    switch (cout) {
+      case 1: resize_store_nhwc<PPT, OUTT, 1>(p, b, hw, q, v); break;
+      case 2: resize_store_nhwc<PPT, OUTT, 2>(p, b, hw, q, v); break;
+      case 3: resize_store_nhwc<PPT, OUTT, 3>(p, b, hw, q, v); break;
+      default: resize_store_nhwc<PPT, OUTT, 4>(p, b, hw, q, v); break;
+    }
+  }
+}
+
+// Bytes of one staged row: LDS byte o of a row is the byte at (row address &
+// ~15) + o, so 16-byte loads stay aligned on both sides; the span starts at
+// most 15 bytes in and its last dword ends at most 3 bytes behind it.
+inline int resize_row_stride(int wmax, int cin) { return (wmax * cin + 15 + 3 + 15) / 16 * 16; }
+
+template <int PPT, int CIN, int OUTT, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void decode_resize_kernel(DecodeParams p, ResizeParams r, int R, int stride) {
+  __shared__ uint32_t tab[kTabWords];
+  extern __shared__ uint4 resize_rows[];   // 2R rows of `stride` bytes
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);   // (the staging barrier below covers the table as well)
+  uint8_t* rows = reinterpret_cast<uint8_t*>(resize_rows);
+
+  const int64_t HW = int64_t(p.H) * p.W;       // source frame
+  const int64_t ohw = int64_t(r.oh) * r.ow;    // output image
+  const int bands = (r.oh + R - 1) / R;
+  const int total = bands * p.B;
+  const int gpr = r.ow / PPT;                  // lane groups per output row
+  const int upr = stride >> 4;                 // 16-byte units per staged row
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cm[k] = p.cmap[k];
+
+  for (int item = blockIdx.x; item < total; item += gridDim.x) {
+    const int b = item / bands;
+    const int i_lo = (item - b * bands) * R;
+    const int nb = min(R, r.oh - i_lo);
+    const int y0 = r.y0[b], x0 = r.x0[b], h = r.h[b], w = r.w[b];
+    const float sy = r.sy[b], sx = r.sx[b];
+    const bool flip = image_flipped(p, b);
+    const bool mirror = (r.mirror_bits >> b) & 1;
+    const uint8_t* img = p.nsrcs ? p.srcs[b] : p.src + (p.src_offsets ? p.src_offsets[b] : int64_t(b) * HW * CIN);
+    // first byte of window row ry's span (flip applied)
+    auto row_addr = [&](int ry) {
+      const int y = y0 + ry;
+      return img + (int64_t(flip ? p.H - 1 - y : y) * p.W + x0) * CIN;
+    };
+    // The window rows the band's taps touch lie in [ymin, ymax].  Up to 2R of
+    // them: staged as that run, row ry in slot ry - ymin (adjacent output
+    // rows share taps).  More (the vertical scale exceeds 2, so no two output
+    // rows share a tap): output row i_lo + n stages just its two taps, in
+    // slots 2n and 2n + 1, and the rows between are never read.
+    const int ymin = resize_axis(i_lo, sy, h).i0;
+    const int run = resize_axis(i_lo + nb - 1, sy, h).i1 - ymin + 1;
+    const bool contig = run <= 2 * R;
+    const int nrows = contig ? run : 2 * nb;
+
+    // Stage: unit e is 16-byte unit q of slot k.  Of a row only the dwords
+    // that hold a byte of its span are read -- CIN == 4: the span itself;
+    // CIN == 3: the span is only byte aligned, and the argument of
+    // load_window_pixels holds: the dword of the first byte and the dword of
+    // the last byte each hold a byte of the span, and as the frame's
+    // H * W * 3 bytes (W % 4 == 0) start on a 16-byte boundary and end on a
+    // dword boundary, neither reaches outside [frame, frame + H * W * CIN).
+    // Four units' loads are issued before the first LDS store.
+    const int units = nrows * upr;
+    // unit e: a 16-byte unit inside the span's dwords is loaded into v (its LDS
+    // byte offset returned), one on the span's edge copied dword by dword
+    auto stage_unit = [&](int e, uint4& v) -> int {
+      if (e >= units) return -1;
+      const int k = e / upr, qb = (e - k * upr) * 16;
+      int ry = ymin + k;
+      if (!contig) {
+        const Axis a = resize_axis(i_lo + (k >> 1), sy, h);
+        ry = (k & 1) ? a.i1 : a.i0;
+      }
+      const uint8_t* ra = row_addr(ry);
+      const int ph = int(reinterpret_cast<uintptr_t>(ra) & 15u);
+      const uint8_t* base = ra - ph;
+      const int lo = ph & ~3, hi = (ph + w * CIN + 3) & ~3;
+      if (qb >= lo && qb + 16 <= hi) {
+        v = *reinterpret_cast<const uint4*>(base + qb);
+        return k * stride + qb;
+      }
+#pragma unroll
+      for (int d = 0; d < 16; d += 4)
+        if (qb + d >= lo && qb + d < hi)
+          *reinterpret_cast<uint32_t*>(rows + k * stride + qb + d) = *reinterpret_cast<const uint32_t*>(base + qb + d);
+      return -1;
+    };
+    for (int e0 = threadIdx.x; e0 < units; e0 += 4 * kBlock) {
+      uint4 v0, v1, v2, v3;
+      const int a0 = stage_unit(e0, v0), a1 = stage_unit(e0 + kBlock, v1);
+      const int a2 = stage_unit(e0 + 2 * kBlock, v2), a3 = stage_unit(e0 + 3 * kBlock, v3);
+      if (a0 >= 0) *reinterpret_cast<uint4*>(rows + a0) = v0;
+      if (a1 >= 0) *reinterpret_cast<uint4*>(rows + a1) = v1;
+      if (a2 >= 0) *reinterpret_cast<uint4*>(rows + a2) = v2;
+      if (a3 >= 0) *reinterpret_cast<uint4*>(rows + a3) = v3;
+    }
+    __syncthreads();
+
+    const int groups = nb * gpr;
+    for (int g = threadIdx.x; g < groups; g += kBlock) {
+      const int li = g / gpr, j = (g - li * gpr) * PPT;
+      const int i = i_lo + li;
+      const Axis ay = resize_axis(i, sy, h);
+      const int k0 = contig ? ay.i0 - ymin : 2 * li, k1 = contig ? ay.i1 - ymin : 2 * li + 1;
+      const uint8_t* t0 = rows + k0 * stride + (reinterpret_cast<uintptr_t>(row_addr(ay.i0)) & 15u);
+      const uint8_t* t1 = rows + k1 * stride + (reinterpret_cast<uintptr_t>(row_addr(ay.i1)) & 15u);
+      int o0[PPT], o1[PPT];
+      float lx0[PPT], lx1[PPT];
+#pragma unroll
+      for (int u = 0; u < PPT; ++u) {
+        const Axis ax = resize_axis(mirror ? r.ow - 1 - (j + u) : j + u, sx, w);
+        o0[u] = ax.i0 * CIN, o1[u] = ax.i1 * CIN, lx0[u] = ax.l0, lx1[u] = ax.l1;
+      }
+      float v[4][PPT];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < cout) {
+          // the pixels' four taps of this channel: bytes, then values (the
+          // table's branches are taken once per channel, as in lookup_static)
+          const int ic = cm[c];
+          uint32_t tb[4 * PPT];
+#pragma unroll
+          for (int u = 0; u < PPT; ++u)
+            tb[4 * u] = t0[o0[u] + ic], tb[4 * u + 1] = t0[o1[u] + ic], tb[4 * u + 2] = t1[o0[u] + ic],
+                   tb[4 * u + 3] = t1[o1[u] + ic];
+          float tv[4 * PPT];
+          resize_values<4 * PPT>(xf, c, tb, tv);
+#pragma unroll
+          for (int u = 0; u < PPT; ++u)
+            v[c][u] = resize_blend(resize_blend(tv[4 * u], tv[4 * u + 1], lx0[u], lx1[u]),
+                                   resize_blend(tv[4 * u + 2], tv[4 * u + 3], lx0[u], lx1[u]), ay.l0, ay.l1);
+        } else {
+#pragma unroll
+          for (int u = 0; u < PPT; ++u) v[c][u] = 0.f;
+        }
+      }
+      resize_store<PPT, OUTT, LAYOUT>(p, b, ohw, cout, int64_t(i) * r.ow + j, v);
+    }
+    __syncthreads();   // the next band of this block restages the rows
+  }
+}
+
+// Fallback: one output pixel per thread, its four taps read from the frame
+// (any size, any alignment, any Cin).
+template <int OUTT>
+__global__ __launch_bounds__(kBlock) void decode_resize_scalar_kernel(DecodeParams p, ResizeParams r) {
+  __shared__ uint32_t tab[kTabWords];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  __syncthreads();
+  const int64_t HW = int64_t(p.H) * p.W;
+  const int64_t ohw = int64_t(r.oh) * r.ow;
+  const int64_t total = ohw * p.B;
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += int64_t(gridDim.x) * kBlock) {
+    const int b = int(g / ohw);
+    const int64_t q = g - int64_t(b) * ohw;
+    const int i = int(q / r.ow), j = int(q - int64_t(i) * r.ow);
+    const Axis ay = resize_axis(i, r.sy[b], r.h[b]);
+    const Axis ax = resize_axis(((r.mirror_bits >> b) & 1) ? r.ow - 1 - j : j, r.sx[b], r.w[b]);
+    const bool flip = image_flipped(p, b);
+    const int ya = int(r.y0[b]) + ay.i0, yb = int(r.y0[b]) + ay.i1;
+    const uint8_t* img = p.nsrcs ? p.srcs[b] : p.src + (p.src_offsets ? p.src_offsets[b] : int64_t(b) * HW * p.Cin);
+    const uint8_t* t0 = img + (int64_t(flip ? p.H - 1 - ya : ya) * p.W + r.x0[b]) * p.Cin;
+    const uint8_t* t1 = img + (int64_t(flip ? p.H - 1 - yb : yb) * p.W + r.x0[b]) * p.Cin;
+    const int o0 = ax.i0 * p.Cin, o1 = ax.i1 * p.Cin;
+    for (int k = 0; k < p.Cout; ++k) {
+      const int ic = p.cmap[k];
+      const float top = resize_blend(xf_value(xf, k, t0[o0 + ic]), xf_value(xf, k, t0[o1 + ic]), ax.l0, ax.l1);
+      const float bot = resize_blend(xf_value(xf, k, t1[o0 + ic]), xf_value(xf, k, t1[o1 + ic]), ax.l0, ax.l1);
+      const float v = resize_blend(top, bot, ay.l0, ay.l1);
+      const int64_t off = p.layout == NCHW ? int64_t(k) * ohw + q : q * p.Cout + k;   // within image b
+      const int64_t ie = ohw * p.Cout;
+      if constexpr (OUTT == OUT_F32) image_out<float>(p, b, ie)[off] = v;
+      else if constexpr (OUTT == OUT_U8) image_out<uint8_t>(p, b, ie)[off] = resize_cvt<OUTT>(v);
+      else image_out<uint16_t>(p, b, ie)[off] = resize_cvt<OUTT>(v);
+    }
+  }
+}
+
+template <int PPT, int CIN, int OUTT>
+void launch_resize_vec(const DecodeParams& p, const ResizeParams& r, int R, int stride, hipStream_t s) {
+  const int items = p.B * ((r.oh + R - 1) / R);
+  const int cap = p.max_grid > 0 ? p.max_grid : 2048;
+  const int grid = items < cap ? items : cap;
+  const size_t lds = size_t(2) * R * stride;
+  if (p.layout == NCHW)
+    decode_resize_kernel<PPT, CIN, OUTT, NCHW><<<grid, kBlock, lds, s>>>(p, r, R, stride);
+  else
+    decode_resize_kernel<PPT, CIN, OUTT, NHWC><<<grid, kBlock, lds, s>>>(p, r, R, stride);
+}
+
+template <int OUTT>
+hipError_t launch_resize_out(const DecodeParams& p, const ResizeParams& r, hipStream_t s) {
+  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  // staged path: decode_crop's conditions on the sources (16-byte aligned
+  // frames; packed RGB rows a whole number of dwords) and on the stores
+  const bool src_aligned = p.nsrcs ? srcs_ok(p.srcs, p.nsrcs, p.B, 16)
+                                   : (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 &&
+                                         (p.src_offsets ? p.src_offsets_aligned != 0
+                                                        : (int64_t(p.H) * p.W * p.Cin) % 16 == 0);
+  const bool dst_aligned = p.ndsts ? dsts_ok(p.dsts, p.ndsts, p.B, 16) : (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0;
+  const bool vec = (r.ow % PPT) == 0 && src_aligned && dst_aligned && (int64_t(r.oh) * r.ow * p.Cout * ELEM) % 16 == 0 &&
+                   (p.Cin == 4 || (p.Cin == 3 && (p.W % 4) == 0));
+  if (!vec) {
+    const int64_t work = int64_t(p.B) * r.oh * r.ow;
+    decode_resize_scalar_kernel<OUTT><<<grid_for(work, p.max_grid), kBlock, 0, s>>>(p, r);
+    return hipGetLastError();
+  }
+  int wmax = 1;
+  for (int b = 0; b < p.B; ++b) wmax = r.w[b] > wmax ? r.w[b] : wmax;
+  const int stride = resize_row_stride(wmax, p.Cin);
+  int R = kResizeBand;
+  while (R > 1 && 2 * R * stride > kResizeRows) R >>= 1;
+  if (2 * R * stride > kResizeRows) return hipErrorInvalidValue;   // a window row too wide to stage twice
+  if (p.Cin == 4)
+    launch_resize_vec<PPT, 4, OUTT>(p, r, R, stride, s);
+  else
+    launch_resize_vec<PPT, 3, OUTT>(p, r, R, stride, s);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t decode_resize(const DecodeParams& p, const ResizeParams& r, hipStream_t stream) {
+  // every condition is checked here and in launch_resize_out, before anything is launched
+  if (p.B < 0 || p.B > kMaxSrcs || p.H <= 0 || p.W <= 0 || r.oh < 1 || r.ow < 1 || r.oh > INT16_MAX || r.ow > INT16_MAX)
+    return hipErrorInvalidValue;
+  for (int b = 0; b < p.B; ++b)
+    if (r.y0[b] < 0 || r.x0[b] < 0 || r.h[b] < 1 || r.w[b] < 1 || int(r.y0[b]) + r.h[b] > p.H ||
+        int(r.x0[b]) + r.w[b] > p.W)
+      return hipErrorInvalidValue;
+  if (p.Cout < 1 || p.Cout > 4 || p.Cin < 1 || p.Cin > 4) return hipErrorInvalidValue;
+  if (p.nsrcs && (p.nsrcs != p.B || !srcs_ok(p.srcs, p.nsrcs, p.B, 1))) return hipErrorInvalidValue;
+  if (p.ndsts && (p.ndsts != p.B || !dsts_ok(p.dsts, p.ndsts, p.B, 1))) return hipErrorInvalidValue;
+  for (int k = 0; k < p.Cout; ++k)
+    if (p.cmap[k] < 0 || p.cmap[k] >= p.Cin) return hipErrorInvalidValue;
+  if (p.B == 0) return hipSuccess;
+  switch (p.out_dtype) {
+    case OUT_F32: return launch_resize_out<OUT_F32>(p, r, stream);
+    case OUT_BF16: return launch_resize_out<OUT_BF16>(p, r, stream);
+    case OUT_F16: return launch_resize_out<OUT_F16>(p, r, stream);
+    case OUT_U8: return launch_resize_out<OUT_U8>(p, r, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
 namespace {
 
 constexpr int delta_ppt(int out_dtype) { return out_dtype == OUT_F32 ? 4 : (out_dtype == OUT_U8 ? 16 : 8); }

@@ -159,6 +159,15 @@ StreamLoader::StreamLoader(const LoaderConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("StreamLoader: bad crop (size >= 1, mirror in [0, 1], x_align 1, 4 or 16)");
   }
   crop_state_ = crop::seed_state(cfg_.crop_seed);
+  if (cfg_.resize) {
+    if (cfg_.crop) throw std::invalid_argument("StreamLoader: a resize does not combine with a crop");
+    if (cfg_.color_matrix) throw std::invalid_argument("StreamLoader: a resize does not combine with the colour kernel");
+    if (cfg_.batch_size > kMaxSrcs) throw std::invalid_argument("StreamLoader: a resize needs batch_size <= 64");
+    if (!resized::valid(cfg_.resize_spec))
+      throw std::invalid_argument(
+          "StreamLoader: bad resize (size 1..32767, 0 < smin <= smax <= 1, rmin <= 1 <= rmax, mirror in [0, 1])");
+  }
+  resize_state_ = resized::seed_state(cfg_.resize_seed);
   mirror_budget_ = mirror::Budget(cfg_.slot_mirror_max_bytes);
   int k = std::max(1, std::min<int>(cfg_.io_threads, int(cfg_.addresses.size())));
   for (int i = 0; i < k; ++i) {
@@ -818,10 +827,18 @@ bool StreamLoader::process(zmtp::Message&& msg) {
       return bad("a " + std::to_string(cfg_.crop_h) + "x" + std::to_string(cfg_.crop_w) + " crop window" + at +
                  " does not fit the stream's " + std::to_string(h) + "x" + std::to_string(w) + " frames");
     }
+    if (cfg_.resize && (!resized::fits(cfg_.resize_spec, h, w) || h > INT16_MAX || w > INT16_MAX)) {
+      const resized::Spec& rs = cfg_.resize_spec;
+      const std::string what = rs.mode == resized::kFixed
+                                   ? "a " + std::to_string(rs.wh) + "x" + std::to_string(rs.ww) + " resize window at (" +
+                                         std::to_string(rs.wy0) + ", " + std::to_string(rs.wx0) + ")"
+                                   : std::string("a resize window");
+      return bad(what + " does not fit the stream's " + std::to_string(h) + "x" + std::to_string(w) + " frames");
+    }
     img_bytes_ = size_t(h) * w * c;
-    // (an identity decode with a crop is no pass-through: it takes the kernel)
+    // (an identity decode with a crop or a resize is no pass-through: it takes the kernel)
     passthrough_ = cfg_.out_dtype == OUT_U8 && cfg_.layout == NHWC && cfg_.cout == c && !cfg_.flip_all &&
-                   !cfg_.color_matrix && !cfg_.crop;
+                   !cfg_.color_matrix && !cfg_.crop && !cfg_.resize;
     for (int k = 0; passthrough_ && k < c; ++k) {
       passthrough_ = cfg_.cmap[k] == k;
       for (int v = 0; passthrough_ && v < 256; ++v) passthrough_ = cfg_.lut[size_t(k) * 256 + size_t(v)] == float(v);
@@ -903,6 +920,10 @@ bool StreamLoader::process(zmtp::Message&& msg) {
   if (cfg_.crop) {
     if (it.tiled) return bad("tile16 frames cannot be cropped (a crop reads raw or rgb_a frames)");
     it.win = crop::draw(crop_state_, crop_spec(), h, w);
+  }
+  if (cfg_.resize) {
+    if (it.tiled) return bad("tile16 frames cannot be resized (a resize reads raw or rgb_a frames)");
+    it.rwin = resized::draw(resize_state_, cfg_.resize_spec, h, w);
   }
   if (cur_.empty()) batch_t0_ = now_ms();
   {
@@ -1039,7 +1060,7 @@ StreamLoader::MappedSegment& StreamLoader::segment(std::string_view name_view) {
 }
 
 bool StreamLoader::mirror_wanted() const {
-  return cfg_.slot_mirror && cfg_.direct && !cfg_.color_matrix && !cfg_.crop && cfg_.decode_streams == 1;
+  return cfg_.slot_mirror && cfg_.direct && !cfg_.color_matrix && !cfg_.crop && !cfg_.resize && cfg_.decode_streams == 1;
 }
 
 // The ring's slot mirror for frames of `cin` stored channels (3: rgb_a slots
@@ -1347,8 +1368,10 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
   }
   const size_t elem = cfg_.color_matrix ? 4 : (cfg_.out_dtype == OUT_F32 ? 4 : (cfg_.out_dtype == OUT_U8 ? 1 : 2));
   const int cout = cfg_.cout;   // (colour kernel: 4, or 3 for RGB jitter)
-  // (with a crop the output image is the window)
-  const size_t out_img_bytes = cfg_.crop ? size_t(cfg_.crop_h) * cfg_.crop_w * cout * elem : size_t(H_) * W_ * cout * elem;
+  // (with a crop the output image is the window, with a resize its output size)
+  const size_t out_img_bytes = cfg_.resize ? size_t(cfg_.resize_spec.oh) * cfg_.resize_spec.ow * cout * elem
+                               : cfg_.crop ? size_t(cfg_.crop_h) * cfg_.crop_w * cout * elem
+                                           : size_t(H_) * W_ * cout * elem;
   uint64_t flips[4] = {0, 0, 0, 0};
   std::vector<const Item*> all;
   all.reserve(size_t(total));
@@ -1536,6 +1559,32 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
         stats_.image_bytes -= whole - window;
       }
     }
+    // resize: likewise through decode_resize, which stages only the rows of
+    // each image's window that its taps touch
+    ResizeParams rsz;
+    rsz.oh = cfg_.resize_spec.oh, rsz.ow = cfg_.resize_spec.ow;
+    auto set_rwindow = [](ResizeParams& r, int n, const Item& it) {
+      const resized::Window& v = it.rwin;
+      r.y0[n] = int16_t(v.y0), r.x0[n] = int16_t(v.x0), r.h[n] = int16_t(v.h), r.w[n] = int16_t(v.w);
+      r.sy[n] = float(v.h) / float(r.oh), r.sx[n] = float(v.w) / float(r.ow);
+      if (v.m) r.mirror_bits |= uint64_t(1) << n;
+    };
+    if (cfg_.resize) {
+      if (total > kMaxSrcs) throw std::runtime_error("StreamLoader: a resize launch holds at most 64 images");
+      for (int i = 0; i < total; ++i) set_rwindow(rsz, i, *all[size_t(i)]);
+      if (direct) {
+        // at most the windows cross the link (an upper bound: once the vertical
+        // scale exceeds 2 the rows between taps are not read either): take back
+        // what process() counted for whole frames
+        uint64_t whole = 0, window = 0;
+        for (const Item* it : all) {
+          whole += it->planar ? uint64_t(H_) * W_ * 3 : uint64_t(img_bytes_);
+          window += uint64_t(it->rwin.h) * it->rwin.w * (it->planar ? 3 : C_);
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        stats_.image_bytes -= whole - window;
+      }
+    }
     // Slot mirror (slot_mirror.h): a plain decode of ring frames reads, per
     // image, only the region its producer reported as rewritten from the host
     // and the rest from the ring's HBM copy, which the same kernel brings up
@@ -1553,7 +1602,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     // that launch takes from the copy was written by earlier, whole reads.
     // reap() / promote_ready() invalidate the slot's entry all the same, so
     // nothing later relies on a copy a torn read produced.
-    const bool mirror_on = plain && !cfg_.crop && mirror_wanted();
+    const bool mirror_on = plain && !cfg_.crop && !cfg_.resize && mirror_wanted();
     auto run_plain = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
       if (!mirror_on) return decode(sp, st);
       // (RGBA -> RGBA u8 NHWC keeps decode()'s 4-pixel host-read shape, kernels.hip launch_out: not mirrored)
@@ -1600,6 +1649,8 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
         std::memset(sp.flip_bits, 0, sizeof(sp.flip_bits));
         CropParams sc;
         sc.h = crop.h, sc.w = crop.w;
+        ResizeParams sr;
+        sr.oh = rsz.oh, sr.ow = rsz.ow;
         int n = 0, i = 0;
         std::vector<const Item*> sub;
         for (auto& b : group)
@@ -1611,11 +1662,12 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
             sp.dsts[n] = static_cast<uint8_t*>(b.dst) + k * out_img_bytes;
             if (it.flip) sp.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
             if (cfg_.crop) set_window(sc, n, it);
+            if (cfg_.resize) set_rwindow(sr, n, it);
             ++n;
           }
         sp.B = sp.nsrcs = sp.ndsts = n;
         sp.Cin = pl == 1 ? 3 : C_;
-        e = cfg_.crop ? decode_crop(sp, sc, st) : run_plain(sp, sub);
+        e = cfg_.resize ? decode_resize(sp, sr, st) : cfg_.crop ? decode_crop(sp, sc, st) : run_plain(sp, sub);
       }
       // (stats_.launches counts launch groups: this one stays one coalesced
       // launch for the batches in it, run as two kernels)
@@ -1632,7 +1684,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       }
       e = decode_tiles(dp, tp, stream_);
     } else {
-      e = cfg_.crop ? decode_crop(dp, crop, st) : run_plain(dp, all);
+      e = cfg_.resize ? decode_resize(dp, rsz, st) : cfg_.crop ? decode_crop(dp, crop, st) : run_plain(dp, all);
     }
   }
   check(e, "decode kernel launch");
@@ -1668,6 +1720,7 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
       if (!it.expanded.empty()) fl.expanded.push_back(std::move(it.expanded));
       if (cfg_.jitter) rb.jitter.insert(rb.jitter.end(), it.jit, it.jit + 4);
       if (cfg_.crop) rb.crop.insert(rb.crop.end(), {it.win.y0, it.win.x0, it.win.m});
+      if (cfg_.resize) rb.window.insert(rb.window.end(), {it.rwin.y0, it.rwin.x0, it.rwin.h, it.rwin.w, it.rwin.m});
       if (it.staged) fl.staged.push_back(std::move(it.staged));
       rb.items.push_back(std::move(it.meta));
     }

@@ -192,6 +192,15 @@ struct LoaderConfig {
   double mirror = 0.0;
   int x_align = 1;
   uint64_t crop_seed = 0;
+  // resized crop (kernels.h: decode_resize): every image is decoded through a
+  // window drawn where the crop window is drawn, in arrival order
+  // (common/crop_draw.h: resized), and resized to resize_spec.oh x .ow; the
+  // batch reports the windows.  As with a crop: at most 64 images per launch,
+  // no slot mirror, no tile16 frames, no colour kernel, no pass-through; not
+  // together with a crop.
+  bool resize = false;
+  resized::Spec resize_spec;
+  uint64_t resize_seed = 0;
 };
 
 // One delivered batch: metadata of each item (non-image bytes of the frame,
@@ -309,6 +318,7 @@ struct ReadyBatch {
   int64_t launch_no = 0;             // host_sync: the launch that read them
   std::vector<float> jitter;         // colour jitter: 4 factors per image (LoaderConfig::jitter)
   std::vector<int32_t> crop;         // crop: (y0, x0, mirrored) per image (LoaderConfig::crop)
+  std::vector<int32_t> window;       // resize: (y0, x0, h, w, mirrored) per image (LoaderConfig::resize)
 };
 
 struct LoaderStats {
@@ -388,6 +398,7 @@ class StreamLoader {
     BufPtr staged;                     // pinned slot a heap-received image was copied into (direct path)
     float jit[4] = {1.f, 1.f, 1.f, 0.f};   // colour-jitter factors (LoaderConfig::jitter)
     crop::Window win;                      // crop window (LoaderConfig::crop)
+    resized::Window rwin;                  // resize window (LoaderConfig::resize)
     BatchMeta meta;
   };
   // rebuild on the host what the batch cannot read in place: a key-frame
@@ -445,6 +456,7 @@ class StreamLoader {
   float* d_mat_ = nullptr;   // 16 matrix + 4 bias (or batch_size x 20: LoaderConfig::matrices)
   uint64_t jit_state_ = 0;   // splitmix64 state of the colour-jitter draws
   uint64_t crop_state_ = 0;  // splitmix64 state of the crop-window draws
+  uint64_t resize_state_ = 0;  // splitmix64 state of the resize-window draws
   crop::Spec crop_spec() const;
   std::vector<Item> cur_;
   std::deque<Pending> pending_;

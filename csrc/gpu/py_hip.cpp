@@ -244,7 +244,7 @@ PYBIND11_MODULE(_hip, m) {
            int Cin, int Cout, std::vector<int> cmap, int flip_all, int out_dtype, int layout, uintptr_t stream,
            bool src_offsets_aligned, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts,
            std::vector<uint64_t> flip_bits, int max_grid, int unroll, std::vector<int> crop_size,
-           std::vector<int> crop) {
+           std::vector<int> crop, std::vector<int> resize_size, std::vector<int> window) {
           DecodeParams p;
           fill_image_lists(p, srcs, dsts, flip_bits, "decode");
           p.max_grid = max_grid;
@@ -260,6 +260,27 @@ PYBIND11_MODULE(_hip, m) {
           p.flip_all = flip_all;
           p.out_dtype = out_dtype;
           p.layout = layout;
+          if (!resize_size.empty()) {
+            // a window of every image resized to resize_size = (oh, ow): window = B x (y0, x0, h, w, mirrored)
+            if (resize_size.size() != 2 || B < 0 || window.size() != size_t(B) * 5 || !crop_size.empty())
+              throw std::invalid_argument(
+                  "decode: resize_size is (oh, ow), window holds (y0, x0, h, w, mirrored) per image, and no crop_size");
+            ResizeParams r;
+            r.oh = resize_size[0], r.ow = resize_size[1];
+            if (B <= kMaxSrcs)   // (decode_resize rejects a larger batch)
+              for (int b = 0; b < B; ++b) {
+                const int* v = &window[size_t(b) * 5];
+                for (int k = 0; k < 4; ++k)
+                  if (v[k] < INT16_MIN || v[k] > INT16_MAX) throw std::invalid_argument("decode: window out of range");
+                r.y0[b] = int16_t(v[0]), r.x0[b] = int16_t(v[1]), r.h[b] = int16_t(v[2]), r.w[b] = int16_t(v[3]);
+                // the fp32 scales of the resize (kernels.h), by IEEE division on the host
+                r.sy[b] = r.oh > 0 ? float(v[2]) / float(r.oh) : 0.f;
+                r.sx[b] = r.ow > 0 ? float(v[3]) / float(r.ow) : 0.f;
+                if (v[4]) r.mirror_bits |= uint64_t(1) << b;
+              }
+            check(decode_resize(p, r, stream_of(stream)), "decode_resize");
+            return;
+          }
           if (crop_size.empty()) {
             check(decode(p, stream_of(stream)), "decode");
             return;
@@ -284,7 +305,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("src_offsets_aligned") = false,
         py::arg("srcs") = std::vector<uintptr_t>(), py::arg("dsts") = std::vector<uintptr_t>(),
         py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0, py::arg("unroll") = 0,
-        py::arg("crop_size") = std::vector<int>(), py::arg("crop") = std::vector<int>());
+        py::arg("crop_size") = std::vector<int>(), py::arg("crop") = std::vector<int>(),
+        py::arg("resize_size") = std::vector<int>(), py::arg("window") = std::vector<int>());
 
   // Region read + slot mirror (kernels.h: decode_delta) at the pointer level: srcs[b] the frame (usually
   // host memory), mirrors[b] its device copy (0: none, the whole image comes from srcs[b]), regions =
@@ -1319,7 +1341,10 @@ PYBIND11_MODULE(_hip, m) {
                        std::vector<float> matrices, std::vector<float> jitter, uint64_t jitter_seed,
                        bool planar_alpha, int decode_streams, std::vector<int> crop, const std::string& crop_mode,
                        std::vector<int> crop_origin, double mirror, int x_align, uint64_t crop_seed,
-                       bool slot_mirror, size_t slot_mirror_max_bytes, size_t slot_mirror_min_frame_bytes) {
+                       bool slot_mirror, size_t slot_mirror_max_bytes, size_t slot_mirror_min_frame_bytes,
+                       std::vector<int> resize, const std::string& resize_mode, std::vector<double> resize_scale,
+                       std::vector<double> resize_ratio, std::vector<int> resize_window, double resize_mirror,
+                       uint64_t resize_seed) {
              LoaderConfig c;
              c.slot_mirror = slot_mirror;
              c.slot_mirror_max_bytes = slot_mirror_max_bytes;
@@ -1378,6 +1403,33 @@ PYBIND11_MODULE(_hip, m) {
                c.x_align = x_align;
                c.crop_seed = crop_seed;
              }
+             // resized crop: resize = (oh, ow); mode 'random' | 'center' | 'full', or 'fixed' with
+             // resize_window = (y0, x0, h, w)
+             if (!resize.empty()) {
+               if (resize.size() != 2) throw std::invalid_argument("StreamLoader: resize = (oh, ow)");
+               btn::resized::Spec& rs = c.resize_spec;
+               c.resize = true;
+               rs.oh = resize[0], rs.ow = resize[1];
+               if (resize_mode == "random") rs.mode = btn::resized::kRandom;
+               else if (resize_mode == "center") rs.mode = btn::resized::kCenter;
+               else if (resize_mode == "full") rs.mode = btn::resized::kFull;
+               else if (resize_mode == "fixed") rs.mode = btn::resized::kFixed;
+               else throw std::invalid_argument("StreamLoader: resize_mode must be 'random', 'center', 'full' or 'fixed'");
+               if (rs.mode == btn::resized::kFixed) {
+                 if (resize_window.size() != 4) throw std::invalid_argument("StreamLoader: resize_window = (y0, x0, h, w)");
+                 rs.wy0 = resize_window[0], rs.wx0 = resize_window[1], rs.wh = resize_window[2], rs.ww = resize_window[3];
+               }
+               if (!resize_scale.empty()) {
+                 if (resize_scale.size() != 2) throw std::invalid_argument("StreamLoader: resize_scale = (smin, smax)");
+                 rs.smin = resize_scale[0], rs.smax = resize_scale[1];
+               }
+               if (!resize_ratio.empty()) {
+                 if (resize_ratio.size() != 2) throw std::invalid_argument("StreamLoader: resize_ratio = (rmin, rmax)");
+                 rs.rmin = resize_ratio[0], rs.rmax = resize_ratio[1];
+               }
+               rs.mirror = resize_mirror;
+               c.resize_seed = resize_seed;
+             }
              return new StreamLoader(c);
            }),
            py::arg("addresses"), py::arg("batch_size"), py::arg("image_key"), py::arg("rcvhwm"),
@@ -1390,7 +1442,10 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("decode_streams") = 1, py::arg("crop") = std::vector<int>(), py::arg("crop_mode") = "random",
            py::arg("crop_origin") = std::vector<int>(), py::arg("mirror") = 0.0, py::arg("x_align") = 1,
            py::arg("crop_seed") = 0, py::arg("slot_mirror") = true,
-           py::arg("slot_mirror_max_bytes") = size_t(1) << 30, py::arg("slot_mirror_min_frame_bytes") = 0)
+           py::arg("slot_mirror_max_bytes") = size_t(1) << 30, py::arg("slot_mirror_min_frame_bytes") = 0,
+           py::arg("resize") = std::vector<int>(), py::arg("resize_mode") = "random",
+           py::arg("resize_scale") = std::vector<double>(), py::arg("resize_ratio") = std::vector<double>(),
+           py::arg("resize_window") = std::vector<int>(), py::arg("resize_mirror") = 0.0, py::arg("resize_seed") = 0)
       .def("start", &StreamLoader::start)
       .def("wait_shape",
            [](StreamLoader& l, long timeout_ms) -> py::object {
@@ -1452,6 +1507,11 @@ PYBIND11_MODULE(_hip, m) {
                py::array_t<int32_t> w({py::ssize_t(rb.crop.size() / 3), py::ssize_t(3)});
                std::memcpy(w.mutable_data(), rb.crop.data(), rb.crop.size() * sizeof(int32_t));
                meta["crop"] = w;
+             }
+             if (!rb.window.empty()) {   // the window (y0, x0, h, w, mirrored) each image was resized from
+               py::array_t<int32_t> w({py::ssize_t(rb.window.size() / 5), py::ssize_t(5)});
+               std::memcpy(w.mutable_data(), rb.window.data(), rb.window.size() * sizeof(int32_t));
+               meta["window"] = w;
              }
              return py::make_tuple(rb.index, meta, rb.recv_ms);
            })

@@ -376,6 +376,39 @@ class NativeError(Exception):
         },
         py::arg("seed"), py::arg("H"), py::arg("W"), py::arg("h"), py::arg("w"), py::arg("mirror"),
         py::arg("x_align"), py::arg("mode"), py::arg("n"), py::arg("origin") = std::pair<int, int>(0, 0));
+  // the windows the stream loader gives its first n images for a resized
+  // crop (common/crop_draw.h: resized): int32 [n, 5] of (y0, x0, h, w, mirrored)
+  m.def("resized_crop_draw",
+        [](uint64_t seed, int H, int W, int oh, int ow, std::pair<double, double> scale,
+           std::pair<double, double> ratio, double mirror, const std::string& mode, int n, std::vector<int> window) {
+          resized::Spec s;
+          s.oh = oh, s.ow = ow, s.mirror = mirror;
+          s.smin = scale.first, s.smax = scale.second, s.rmin = ratio.first, s.rmax = ratio.second;
+          if (mode == "random") s.mode = resized::kRandom;
+          else if (mode == "center") s.mode = resized::kCenter;
+          else if (mode == "full") s.mode = resized::kFull;
+          else if (mode == "fixed") s.mode = resized::kFixed;
+          else throw std::invalid_argument("resized_crop_draw: mode must be 'random', 'center', 'full' or 'fixed'");
+          if (s.mode == resized::kFixed) {
+            if (window.size() != 4) throw std::invalid_argument("resized_crop_draw: window = (y0, x0, h, w)");
+            s.wy0 = window[0], s.wx0 = window[1], s.wh = window[2], s.ww = window[3];
+          }
+          if (n < 0 || !resized::valid(s)) throw std::invalid_argument("resized_crop_draw: bad n, size, scale, ratio or mirror");
+          if (!resized::fits(s, H, W))
+            throw std::invalid_argument("resized_crop_draw: a " + std::to_string(s.wh) + "x" + std::to_string(s.ww) +
+                                        " window at (" + std::to_string(s.wy0) + ", " + std::to_string(s.wx0) +
+                                        ") does not fit a " + std::to_string(H) + "x" + std::to_string(W) + " frame");
+          py::array_t<int32_t> out({py::ssize_t(n), py::ssize_t(5)});
+          int32_t* o = out.mutable_data();
+          uint64_t state = resized::seed_state(seed);
+          for (int i = 0; i < n; ++i) {
+            const resized::Window win = resized::draw(state, s, H, W);
+            o[5 * i] = win.y0, o[5 * i + 1] = win.x0, o[5 * i + 2] = win.h, o[5 * i + 3] = win.w, o[5 * i + 4] = win.m;
+          }
+          return out;
+        },
+        py::arg("seed"), py::arg("H"), py::arg("W"), py::arg("oh"), py::arg("ow"), py::arg("scale"), py::arg("ratio"),
+        py::arg("mirror"), py::arg("mode"), py::arg("n"), py::arg("window") = std::vector<int>());
   m.def("btr_header", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> offs) {
     std::vector<int64_t> o(offs.data(), offs.data() + offs.size());
     auto h = codec::btr_header(o);

@@ -67,7 +67,10 @@ class DeviceLoader:
     decode: DecodeConfig
         What the decode kernel does (channels, gamma, normalisation, dtype,
         layout, flip, optional colour matrix or jitter, optional crop +
-        mirror: ``batch['crop']`` then reports each image's window).
+        mirror: ``batch['crop']`` then reports each image's window; or an
+        optional resized crop, ``DecodeConfig(resize=ops.ResizedCrop(...))``:
+        ``batch['window']`` then reports each image's (y0, x0, h, w,
+        mirrored) as int32 [B, 5], and there is no ``batch['crop']``).
     device: torch.device / int / str
         Target GPU (default: current device).
     max_items: int, optional
@@ -279,6 +282,12 @@ class DeviceLoader:
             c = cfg.crop
             crop = dict(crop=list(c.size), crop_mode=c.kind, crop_origin=list(c.origin or ()), mirror=c.mirror,
                         x_align=c.x_align, crop_seed=c.seed & ((1 << 64) - 1))
+        # resized crop inside the decode: windows drawn per image in the loader (batch['window'])
+        if cfg.resize is not None:
+            r = cfg.resize
+            crop = dict(resize=list(r.size), resize_mode=r.kind, resize_scale=list(r.scale), resize_ratio=list(r.ratio),
+                        resize_window=list(r.window or ()), resize_mirror=r.mirror,
+                        resize_seed=r.seed & ((1 << 64) - 1))
         max_batches = -1 if self.max_items is None else self.max_items // self.batch_size
         return ext.StreamLoader(
             self.addresses, self.batch_size, self.image_key, self.rcvhwm, self.io_threads, self.device.index,

@@ -261,6 +261,12 @@ class DeviceReplayBuffer:
         ops._check_windows(win.astype(np.int64), crop, H, W)
         return np.ascontiguousarray(win, dtype=np.int32)
 
+    @staticmethod
+    def _no_resize(decode: DecodeConfig):
+        if decode.resize is not None:
+            raise ValueError('DeviceReplayBuffer: a resize is not supported on the replay path; '
+                             'use ops.decode(store[index], cfg, window=windows)')
+
     def gather(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig(), windows=None, _counter=None):
         """Decoded frames ``idx`` (device int tensor) + their metadata.  On a
         GPU: one fused launch decodes the frames and gathers every metadata
@@ -275,6 +281,7 @@ class DeviceReplayBuffer:
         if self._size == 0:
             raise IndexError('empty replay buffer')
         idx = idx.to(self.device, torch.int64)
+        self._no_resize(decode)
         crop = decode.crop
         if crop is None:
             if windows is not None:
@@ -320,6 +327,7 @@ class DeviceReplayBuffer:
         batches.  With a ``generator`` only the indices come from it."""
         if self._size == 0:
             raise IndexError('empty replay buffer')
+        self._no_resize(decode)
         if generator is None and self._fused(decode):
             ctr = _counter
             if ctr is None:

@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 __all__ = [
-    'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'philox_windows', 'replay_windows', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
+    'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'ResizedCrop', 'resized_windows', 'resized_crop_points', 'philox_windows', 'replay_windows', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
     'color4x4',
     'project', 'adaptive_avg_pool_nhwc', 'AdaptiveAvgPool2d', 'batch_norm_leaky_relu', 'BatchNormLeakyReLU2d',
     'reference_decode', 'reference_color4x4', 'reference_project', 'reference_gamma',
@@ -313,6 +313,208 @@ def crop_points(xy, crop, size):
     return stack([x, xy[..., 1] - y0], -1)
 
 
+@dataclasses.dataclass(frozen=True)
+class ResizedCrop:
+    """Random resized crop (and Resize / CenterCrop) inside the fused decode.
+
+    Every image is decoded through an ``h x w`` window of the upright frame,
+    resized to ``size = (oh, ow)`` and then optionally mirrored left-right.
+    The resize is bilinear with half-pixel centres and no antialiasing -- the
+    mathematics of ``F.interpolate(mode='bilinear', align_corners=False)`` --
+    with every fp32 operation rounded on its own (:func:`reference_decode` is
+    the bit-exact oracle).  The kernel reads only the window's rows that the
+    taps touch, in runs, in place (csrc/gpu/kernels.h: ``decode_resize``).
+
+    size: ``(oh, ow)``, 1..32767.
+    scale: ``(smin, smax)``, the window's share of the frame's area,
+        ``0 < smin <= smax <= 1`` (random mode).
+    ratio: ``(rmin, rmax)``, ``w / h`` of the window, ``rmin <= 1 <= rmax``
+        (random mode).
+    mode: ``'random'`` (default): window and mirror bit drawn per image from a
+        seeded stream in arrival order (:func:`resized_windows`);
+        ``'center'``: the largest centred window of the output's aspect
+        (Resize + CenterCrop); ``'full'``: the whole frame (a plain Resize).
+    window: ``(y0, x0, h, w)``: a fixed window, never mirrored (``mode`` is
+        ignored).
+    mirror: probability of a mirrored output, in [0, 1] (random mode only).
+    seed: seed of the stream (seeded like the crop's, with a constant of its
+        own: the crop, jitter and resize streams never share a state).
+
+    The sampler is deliberately NOT torchvision's ``RandomResizedCrop``: it
+    takes a fixed number of draws per image (five), it clamps a window that
+    exceeds the frame instead of rejecting and redrawing it, and the aspect is
+    piecewise reciprocal-uniform about 1 (uniform in ``[1, rmax]`` with
+    probability 1/2, else the reciprocal of a uniform in ``[1, 1 / rmin]``),
+    not log-uniform.  It uses only +, -, *, / and sqrt in double, so the
+    native draw and :func:`resized_windows` agree bit for bit.
+
+    The stream loader reports each batch's windows as ``batch['window']``
+    (int32 [B, 5]: y0, x0, h, w, mirrored) and does not touch the metadata:
+    :func:`resized_crop_points` maps pixel coordinates into the output.
+    Limits: at most 64 images per launch; not with the colour-kernel options,
+    tile16 frames, the slot mirror or the replay path (``decode_gather``,
+    ``replay_sample``, ``DeviceReplayBuffer``); downscaling does not
+    antialias.  The reference has no such stage.
+    """
+    size: Sequence[int]
+    scale: Sequence[float] = (0.08, 1.0)
+    ratio: Sequence[float] = (3.0 / 4.0, 4.0 / 3.0)
+    mode: str = 'random'
+    window: Optional[Sequence[int]] = None
+    mirror: float = 0.0
+    seed: int = 0
+
+    def __post_init__(self):
+        try:
+            size = tuple(int(v) for v in self.size)
+        except TypeError:
+            raise ValueError('ResizedCrop.size must be (oh, ow)') from None
+        if len(size) != 2 or min(size) < 1 or max(size) > 32767:
+            raise ValueError('ResizedCrop.size must be (oh, ow) with 1 <= oh, ow <= 32767')
+        object.__setattr__(self, 'size', size)
+        try:
+            scale = tuple(float(v) for v in self.scale)
+            ratio = tuple(float(v) for v in self.ratio)
+        except TypeError:
+            raise ValueError('ResizedCrop.scale and ratio must be pairs') from None
+        if len(scale) != 2 or not 0.0 < scale[0] <= scale[1] <= 1.0:
+            raise ValueError('ResizedCrop.scale must be (smin, smax) with 0 < smin <= smax <= 1')
+        if len(ratio) != 2 or not 0.0 < ratio[0] <= 1.0 <= ratio[1] or ratio[1] == float('inf'):
+            raise ValueError('ResizedCrop.ratio must be (rmin, rmax) with 0 < rmin <= 1 <= rmax')
+        object.__setattr__(self, 'scale', scale)
+        object.__setattr__(self, 'ratio', ratio)
+        if self.mode not in ('random', 'center', 'full'):
+            raise ValueError("ResizedCrop.mode must be 'random', 'center' or 'full'")
+        if self.window is not None:
+            try:
+                window = tuple(int(v) for v in self.window)
+            except TypeError:
+                raise ValueError('ResizedCrop.window must be (y0, x0, h, w)') from None
+            if len(window) != 4 or window[0] < 0 or window[1] < 0 or window[2] < 1 or window[3] < 1 \
+                    or window[0] + window[2] > 32767 or window[1] + window[3] > 32767:
+                raise ValueError('ResizedCrop.window must be (y0, x0, h, w) with y0, x0 >= 0, h, w >= 1 '
+                                 'inside 32767 pixels')
+            object.__setattr__(self, 'window', window)
+        if not 0.0 <= float(self.mirror) <= 1.0:
+            raise ValueError('ResizedCrop.mirror must be a probability in [0, 1]')
+        object.__setattr__(self, 'mirror', float(self.mirror))
+        if self.mirror and self.kind != 'random':
+            raise ValueError("ResizedCrop.mirror is drawn per image: it needs mode 'random' and no fixed window")
+        object.__setattr__(self, 'seed', int(self.seed))
+
+    @property
+    def kind(self):
+        """'fixed' with a window, else the mode."""
+        return 'fixed' if self.window is not None else self.mode
+
+    def check_frame(self, H, W):
+        """ValueError unless every window lies inside an H x W frame (only a fixed one can leave it)."""
+        if H < 1 or W < 1 or H > 32767 or W > 32767:
+            raise ValueError(f'a {H}x{W} frame cannot be resized (1..32767 pixels a side)')
+        if self.window is not None:
+            y0, x0, h, w = self.window
+            if y0 + h > H or x0 + w > W:
+                raise ValueError(f'a {h}x{w} resize window at {(y0, x0)} does not fit a {H}x{W} frame')
+
+
+def resized_windows(rc: ResizedCrop, H: int, W: int, n: int) -> np.ndarray:
+    """int32 [n, 5]: the windows (y0, x0, h, w, mirrored) the stream loader
+    gives its first ``n`` images of H x W frames (csrc/common/crop_draw.h:
+    ``resized``; ``_native.resized_crop_draw`` is the same function natively).
+
+    ``'full'``: the frame.  ``'center'``: with ``(oh, ow) = rc.size``,
+    ``h = H, w = max(1, H*ow // oh)`` if ``W*oh >= H*ow`` else
+    ``w = W, h = max(1, W*oh // ow)``, centred (rounded down).  ``'random'``:
+    five splitmix64 words z1..z5 per image; with ``u(z) = (z >> 11) * 2**-53``,
+    in double::
+
+        s = smin + u(z1) * (smax - smin)
+        v = 2 * u(z2);  r = 1 + v * (rmax - 1) if v < 1 else 1 / (1 + (v - 1) * (1 / rmin - 1))
+        A = s * float(H * W)
+        w = clamp(int(floor(sqrt(A * r) + 0.5)), 1, W);  h = clamp(int(floor(sqrt(A / r) + 0.5)), 1, H)
+        y0 = ((z3 >> 32) * (H - h + 1)) >> 32;  x0 = ((z4 >> 32) * (W - w + 1)) >> 32
+        m  = (z5 >> 40) < int(mirror * 2**24)
+    """
+    import math
+    rc.check_frame(H, W)
+    oh, ow = rc.size
+    out = np.zeros((n, 5), np.int32)
+    if rc.kind == 'fixed':
+        out[:, :4] = rc.window
+        return out
+    if rc.kind == 'full':
+        out[:, 2], out[:, 3] = H, W
+        return out
+    if rc.kind == 'center':
+        if W * oh >= H * ow:
+            h, w = H, max(1, H * ow // oh)
+        else:
+            h, w = max(1, W * oh // ow), W
+        out[:] = ((H - h) // 2, (W - w) // 2, h, w, 0)
+        return out
+    M64 = (1 << 64) - 1
+    state = (rc.seed * 0x9E3779B97F4A7C15 + 0xA0761D6478BD642F) & M64
+
+    def draw():
+        nonlocal state
+        state = (state + 0x9E3779B97F4A7C15) & M64
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+        return z ^ (z >> 31)
+
+    def u():
+        return float(draw() >> 11) * (1.0 / 9007199254740992.0)
+    (smin, smax), (rmin, rmax) = rc.scale, rc.ratio
+    thresh = int(rc.mirror * 16777216.0)
+    for i in range(n):
+        s = smin + u() * (smax - smin)
+        v = 2.0 * u()
+        r = 1.0 + v * (rmax - 1.0) if v < 1.0 else 1.0 / (1.0 + (v - 1.0) * (1.0 / rmin - 1.0))
+        A = s * float(H * W)
+        w = min(W, max(1, int(math.floor(math.sqrt(A * r) + 0.5))))
+        h = min(H, max(1, int(math.floor(math.sqrt(A / r) + 0.5))))
+        y0 = ((draw() >> 32) * (H - h + 1)) >> 32
+        x0 = ((draw() >> 32) * (W - w + 1)) >> 32
+        out[i] = (y0, x0, h, w, (draw() >> 40) < thresh)
+    return out
+
+
+def resized_crop_points(xy, windows, size):
+    """Map pixel coordinates of the full frame into resized-crop outputs.
+
+    xy: numpy array or torch tensor [B, ..., 2] of (x, y); windows: the
+    [B, 5] windows (``batch['window']``); size: the output's (oh, ow).
+    Returns ``x' = (x - x0 + 0.5) * ow / w - 0.5`` (``ow - 1 - x'`` for a
+    mirrored window) and ``y' = (y - y0 + 0.5) * oh / h - 0.5``, as the type
+    of ``xy`` (the half-pixel convention of the resize: a source pixel centre
+    maps to where the resize samples it).  Points outside the window keep
+    coordinates outside ``[-0.5, ow - 0.5) x [-0.5, oh - 0.5)``."""
+    oh, ow = int(size[0]), int(size[1])
+    is_np = isinstance(xy, np.ndarray) or not hasattr(xy, 'new_tensor')
+    if is_np:
+        xy = np.asarray(xy)
+        if not np.issubdtype(xy.dtype, np.floating):
+            xy = xy.astype(np.float64)
+        win = np.asarray(windows).reshape(-1, 5).astype(xy.dtype)
+        where, stack = np.where, np.stack
+    else:
+        import torch
+        if not xy.is_floating_point():
+            xy = xy.to(torch.float32)
+        win = torch.as_tensor(np.asarray(windows) if not isinstance(windows, torch.Tensor) else windows).reshape(-1, 5)
+        win = win.to(device=xy.device, dtype=xy.dtype)
+        where, stack = torch.where, torch.stack
+    if xy.shape[0] != win.shape[0] or xy.shape[-1] != 2:
+        raise ValueError('resized_crop_points: xy is [B, ..., 2] with one window per leading index')
+    shape = (win.shape[0],) + (1,) * (xy.ndim - 2)
+    y0, x0, h, w, m = (win[:, k].reshape(shape) for k in range(5))
+    x = (xy[..., 0] - x0 + 0.5) * ow / w - 0.5
+    x = where(m != 0, (ow - 1) - x, x)
+    y = (xy[..., 1] - y0 + 0.5) * oh / h - 0.5
+    return stack([x, y], -1)
+
+
 _LUMA = np.array([0.213, 0.715, 0.072])
 
 
@@ -362,6 +564,9 @@ class DecodeConfig:
     crop: a :class:`Crop` -- every image is decoded through a window (and
         optionally mirrored); the output has the window's size.  Not with the
         colour-kernel options (color_matrix, color_matrices, color_jitter).
+    resize: a :class:`ResizedCrop` -- every image is decoded through a window
+        resized (bilinear) to ``resize.size`` and optionally mirrored; the
+        output has that size.  Not with ``crop`` or the colour-kernel options.
     """
     channels: object = 'rgb'
     gamma: Optional[float] = None
@@ -377,6 +582,7 @@ class DecodeConfig:
     color_biases: Optional[Sequence] = None
     color_jitter: Optional[ColorJitter] = None
     crop: Optional[Crop] = None
+    resize: Optional[ResizedCrop] = None
 
     def __post_init__(self):
         # normalise sequences to tuples: configs are hashable cache keys
@@ -425,6 +631,13 @@ class DecodeConfig:
                 raise TypeError('crop must be an ops.Crop')
             if self.colour_kernel:
                 raise ValueError('crop does not combine with color_matrix, color_matrices or color_jitter')
+        if self.resize is not None:
+            if not isinstance(self.resize, ResizedCrop):
+                raise TypeError('resize must be an ops.ResizedCrop')
+            if self.crop is not None:
+                raise ValueError('resize does not combine with crop (a ResizedCrop has a window of its own)')
+            if self.colour_kernel:
+                raise ValueError('resize does not combine with color_matrix, color_matrices or color_jitter')
 
     # -- presets -----------------------------------------------------------
     @classmethod
@@ -467,9 +680,13 @@ class DecodeConfig:
         return float(j.pivot) if j is not None and j.pivot is not None else 127.5 * float(self.scale)
 
     def out_shape(self, B, H, W):
-        """Shape of B decoded H x W frames (with a crop: B windows; ValueError
-        when the window does not fit the frame)."""
+        """Shape of B decoded H x W frames (with a crop: B windows, with a
+        resize: B outputs of ``resize.size``; ValueError when the window does
+        not fit the frame)."""
         c = self.cout
+        if self.resize is not None:
+            self.resize.check_frame(H, W)
+            H, W = self.resize.size
         if self.crop is not None:
             self.crop.check_frame(H, W)
             H, W = self.crop.size
@@ -630,13 +847,79 @@ def _crop_rows(crop, B):
     return [tuple(int(v) for v in r) for r in win]
 
 
-def reference_decode(images, cfg: DecodeConfig, flip=None, jitter=None, crop=None):
+def _window_rows(window, B):
+    """The [B, 5] resize windows as a list of int 5-tuples (one window (5,) or (4,) serves every image)."""
+    if window is None:
+        raise ValueError('a resize config needs the batch\'s windows: window=[B, 5] of (y0, x0, h, w, mirrored)')
+    if hasattr(window, 'detach'):
+        window = window.detach().cpu().numpy()
+    win = np.asarray(window)
+    if win.ndim == 1 and win.shape[0] in (4, 5):
+        win = np.tile(np.concatenate([win, np.zeros(5 - win.shape[0], win.dtype)]), (B, 1))
+    if win.shape != (B, 5):
+        raise ValueError(f'window must be [{B}, 5] (y0, x0, h, w, mirrored), not {list(win.shape)}')
+    return [tuple(int(v) for v in r) for r in win]
+
+
+def _resize_axis(n_in, n_out, device):
+    """(i0, i1, l0, l1) of every output index of one axis: the fp32 arithmetic of csrc/gpu/kernels.h
+    (decode_resize), every operation a torch elementwise op of its own."""
+    import torch
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    d = torch.arange(n_out, dtype=torch.float32)
+    s = torch.clamp((d + 0.5) * scale - 0.5, min=0.0)
+    i0 = s.floor().to(torch.int64).clamp(max=n_in - 1)
+    i1 = (i0 + 1).clamp(max=n_in - 1)
+    l1 = s - i0.to(torch.float32)
+    l0 = 1.0 - l1
+    return i0.to(device), i1.to(device), l0.to(device), l1.to(device)
+
+
+def _reference_resize(win, oh, ow):
+    """Bilinear resize of fp32 ``win`` [C, h, w] to [C, oh, ow]: rows blended horizontally first, then
+    vertically, every fp32 operation rounded on its own."""
+    y0, y1, ly0, ly1 = _resize_axis(win.shape[-2], oh, win.device)
+    x0, x1, lx0, lx1 = _resize_axis(win.shape[-1], ow, win.device)
+
+    def row(r):
+        a = win[:, r, :]
+        return a[..., x0] * lx0 + a[..., x1] * lx1
+    top, bot = row(y0), row(y1)
+    return top * ly0[:, None] + bot * ly1[:, None]
+
+
+def reference_decode(images, cfg: DecodeConfig, flip=None, jitter=None, crop=None, window=None):
     """fp32 PyTorch reference of :func:`decode` (images: u8 [B,H,W,C]); for a
     ``color_jitter`` config, ``jitter`` holds the [B, 4] factors of the batch
     (``batch['color_jitter']``); for a ``crop`` config, ``crop`` holds its
     [B, 3] windows (``batch['crop']``): the uncropped reference, sliced and
-    mirrored."""
+    mirrored; for a ``resize`` config, ``window`` holds its [B, 5] windows
+    (``batch['window']``): the uncropped fp32 reference, sliced, resized with
+    the arithmetic of csrc/gpu/kernels.h (``decode_resize``) in torch fp32
+    elementwise ops, mirrored, then converted to the output dtype (bf16 / f16
+    to nearest even, uint8 as ``clamp(rint(r), 0, 255)``)."""
     import torch
+    if cfg.resize is not None:
+        if crop is not None:
+            raise ValueError('crop windows given for a config without a crop')
+        full = reference_decode(images, dataclasses.replace(cfg, resize=None, dtype='float32', layout='nchw'),
+                                flip=flip, jitter=jitter)
+        H, W = full.shape[2], full.shape[3]
+        oh, ow = cfg.resize.size
+        outs = []
+        for b, (y0, x0, h, w, m) in enumerate(_window_rows(window, full.shape[0])):
+            if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+                raise ValueError(f'resize window {(y0, x0)} + {(h, w)} leaves the {H}x{W} frame')
+            o = _reference_resize(full[b, :, y0:y0 + h, x0:x0 + w], oh, ow)
+            outs.append(torch.flip(o, dims=[2]) if m else o)
+        out = torch.stack(outs)
+        if cfg.dtype == 'uint8':
+            out = torch.round(out).clamp(0, 255)
+        if cfg.layout == 'nhwc':
+            out = out.permute(0, 2, 3, 1).clone(memory_format=torch.contiguous_format)   # (dense strides for C == 1 too)
+        return out.to(cfg.torch_dtype())
+    if window is not None:
+        raise ValueError('resize windows given for a config without a resize')
     if cfg.crop is not None:
         full = reference_decode(images, dataclasses.replace(cfg, crop=None), flip=flip, jitter=jitter)
         h, w = cfg.crop.size
@@ -776,10 +1059,13 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None, crop=None):
+def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None, crop=None, window=None):
     """Fused decode of a u8 [B,H,W,C] device tensor with the gfx950 kernel.
     For a ``crop`` config, ``crop`` holds the [B, 3] windows (y0, x0,
-    mirrored) of the batch, e.g. from :func:`crop_windows` (B <= 64)."""
+    mirrored) of the batch, e.g. from :func:`crop_windows` (B <= 64).  For a
+    ``resize`` config, ``window`` holds the [B, 5] windows (y0, x0, h, w,
+    mirrored), e.g. from :func:`resized_windows` (B <= 64; one window of 4 or
+    5 values serves every image)."""
     import torch
     if cfg.crop is not None:
         cfg.crop.no_pad('decode')
@@ -819,6 +1105,18 @@ def decode(images, cfg: DecodeConfig = DecodeConfig(), flip=None, out=None, crop
         kw = dict(crop_size=list(cfg.crop.size), crop=[v for r in _crop_rows(crop, B) for v in r])
     elif crop is not None:
         raise ValueError('crop windows given for a config without a crop')
+    if cfg.resize is not None:
+        if B > 64:
+            raise ValueError('decode: a resize config takes at most 64 images per call')
+        if tuple(out.shape) != tuple(cfg.out_shape(B, H, W)) or not out.is_contiguous():
+            raise ValueError('decode: out must be a contiguous tensor of the resized shape')
+        rows = _window_rows(window, B)
+        for y0, x0, h, w, _ in rows:
+            if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+                raise ValueError(f'decode: resize window {(y0, x0)} + {(h, w)} leaves the {H}x{W} frame')
+        kw = dict(resize_size=list(cfg.resize.size), window=[v for r in rows for v in r])
+    elif window is not None:
+        raise ValueError('resize windows given for a config without a resize')
     ext.decode(x.data_ptr(), 0, out.data_ptr(), lut.data_ptr(), fl, B, H, W, C, cfg.cout, cfg.cmap,
                int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], _stream(x.device), **kw)
     return out
@@ -837,6 +1135,8 @@ def decode_gather(store, index, cfg: DecodeConfig = DecodeConfig(), out=None):
         raise ValueError('decode_gather: colour matrices are not supported; use color4x4 on store[index]')
     if cfg.crop is not None:
         raise ValueError('decode_gather: crops are not supported; use decode(store[index], cfg, crop=windows)')
+    if cfg.resize is not None:
+        raise ValueError('decode_gather: a resize is not supported; use decode(store[index], cfg, window=windows)')
     N, H, W, C = store.shape
     if max(cfg.cmap) >= C:
         raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
@@ -959,6 +1259,9 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
         raise TypeError('replay_sample expects a contiguous uint8 [N,H,W,C] device tensor')
     if cfg.colour_kernel:
         raise ValueError('replay_sample does not apply colour matrices (use gather + color4x4)')
+    if cfg.resize is not None:
+        raise ValueError('replay_sample: a resize is not supported on the replay path; '
+                         'use decode(store[index], cfg, window=windows)')
     N, H, W, C = store.shape
     if max(cfg.cmap) >= C:
         raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
