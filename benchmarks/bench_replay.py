@@ -24,6 +24,84 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / 'pytorch-blender_amd'))
 
 
+def bench_stack(a, rb, cfg, fill_s):
+    """--stack K: three ways to a batch of K-frame transitions, timed in this process, two rounds each."""
+    import numpy as np
+    import torch
+    from blendtorch import ops
+    dev, B, K, S = rb.device, a.batch, a.stack, a.stride
+    cap, crop = rb.capacity, cfg.crop
+    H, W, C = rb.frame_shape
+    kw = dict(stack=K, stride=S, next_keys=('reward',))
+    # (a) ONE launch (two graph nodes with --graph: the sample and the counter advance)
+    fused = rb.graphed_transition_sampler(B, cfg, **kw) if a.graph else (lambda: rb.sample_transitions(B, cfg, **kw))
+    rng = np.random.default_rng(0)
+
+    # (b) what the parent API offers: 2K gathers (one window per stack, uploaded from the host), two cats and
+    # the successor's metadata.  It does not look at episode starts, which only makes it cheaper; the given
+    # windows are a host upload, so it cannot be captured: it runs eagerly also with --graph
+    def composed():
+        anchor = torch.randint(S, len(rb) - S, (B,), device=dev)
+        wins = [None, None]
+        if crop is not None:
+            h, w = crop.size
+            wins = [np.stack([rng.integers(-crop.pad, H + crop.pad - h + 1, B), rng.integers(-crop.pad, W + crop.pad - w + 1, B),
+                              rng.integers(0, 2, B) * (crop.mirror > 0)], axis=1) for _ in range(2)]
+        sides, out = [], {}
+        for d in (0, 1):
+            planes = []
+            for f in range(K):
+                g = rb.gather((anchor - (K - 1 - f - d) * S) % cap, cfg, **({} if crop is None else dict(windows=wins[d])))
+                planes.append(g['image'])
+                if d == 0 and f == K - 1:
+                    out.update({k: v for k, v in g.items() if k != 'image'})
+            sides.append(torch.cat(planes, dim=1))
+        out.update(obs=sides[0], next_obs=sides[1], next_reward=rb.meta['reward'].index_select(0, (anchor + S) % cap))
+        return out
+
+    # (c) the equal-bytes floor: the plain (cropped) sample of 2 K B images, in launches of at most 1024
+    n, parts = 2 * K * B, []
+    while n:
+        parts.append(min(n, 1024))
+        n -= parts[-1]
+    plain = [rb.graphed_sampler(p, cfg) if a.graph else (lambda p=p: rb.sample(p, cfg)) for p in parts]
+
+    def floor():
+        return [s() for s in plain]
+
+    rows = {'fused transitions': fused, 'composed gathers': composed, 'equal-bytes sample': floor}
+    times = {k: [] for k in rows}
+    for _ in range(2):
+        for name, fn in rows.items():
+            for _ in range(a.warmup):
+                fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                b = fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / a.steps * 1e6)
+            del b
+    us = {k: min(v) for k, v in times.items()}
+    for name, v in times.items():
+        print(f'{name:20s} {us[name]:10.2f} us/batch   (rounds: {", ".join("%.2f" % t for t in v)})', flush=True)
+    print(f'fused / composed     {us["fused transitions"] / us["composed gathers"]:10.3f}', flush=True)
+    print(f'fused / equal-bytes  {us["fused transitions"] / us["equal-bytes sample"]:10.3f}', flush=True)
+    h, w = (H, W) if crop is None else crop.size
+    moved = 2 * K * B * h * w * (C + cfg.cout * (4 if a.dtype == 'float32' else 2))
+    print(json.dumps({'metric': 'replay transitions us/batch (HBM store -> stacked obs, next_obs)',
+                      'value': round(us['fused transitions'], 2), 'unit': 'us/batch', 'batch': B, 'stack': K,
+                      'stride': S, 'graph': a.graph, 'dtype': a.dtype, 'frame': [H, W, C], 'frames': a.frames,
+                      'us_per_batch': {k: round(v, 2) for k, v in us.items()},
+                      'rounds_us': {k: [round(t, 2) for t in v] for k, v in times.items()},
+                      'fused_over_composed': round(us['fused transitions'] / us['composed gathers'], 3),
+                      'fused_over_equal_bytes': round(us['fused transitions'] / us['equal-bytes sample'], 3),
+                      'effective_tbps': round(moved / us['fused transitions'] / 1e6, 3), 'equal_bytes_launches': parts,
+                      'fill_s': round(fill_s, 2),
+                      'crop': None if crop is None else {'size': list(crop.size), 'pad': crop.pad,
+                                                         'mirror': crop.mirror}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=4096)
@@ -40,11 +118,21 @@ def main():
                     help='sample through random H x W windows (fused sampler only)')
     ap.add_argument('--pad', type=int, default=0, help='replicate padding of the crop (random shift)')
     ap.add_argument('--mirror', type=float, default=0.0, help='probability of a mirrored window')
+    ap.add_argument('--stack', type=int, default=0, metavar='K',
+                    help='frame-stacked transitions: time the fused sample_transitions, the composed path '
+                         '(2K gathers + cat) and the equal-bytes plain sample (synthetic fill)')
+    ap.add_argument('--stride', type=int, default=1, metavar='S', help='frames per environment step (--stack)')
+    ap.add_argument('--frame', type=int, nargs=3, metavar=('H', 'W', 'C'), default=(480, 640, 4),
+                    help='frame shape of the synthetic store')
     a = ap.parse_args()
     if a.crop is None and (a.pad or a.mirror):
         ap.error('--pad and --mirror need --crop')
     if a.crop is not None and a.sampler != 'fused':
         ap.error('--crop needs the fused sampler')
+    if a.stack and (a.fill != 'synthetic' or a.sampler != 'fused'):
+        ap.error('--stack needs the synthetic fill and the fused sampler')
+    if a.fill != 'synthetic' and tuple(a.frame) != (480, 640, 4):
+        ap.error('--frame needs the synthetic fill')
 
     import torch
     from blendtorch import btt, ops
@@ -54,10 +142,14 @@ def main():
     t0 = time.perf_counter()
     if a.fill == 'synthetic':
         g = torch.Generator(device=dev).manual_seed(0)
+        fh, fw, fc = a.frame
         for s in range(0, a.frames, 256):
             n = min(256, a.frames - s)
-            rb.extend(torch.randint(0, 256, (n, 480, 640, 4), dtype=torch.uint8, device=dev, generator=g),
-                      frameid=torch.arange(s, s + n, device=dev))
+            ids = torch.arange(s, s + n, device=dev)
+            meta = {'frameid': ids}
+            if a.stack:   # an episode starts every 100 steps of every environment
+                meta.update(first=((ids // a.stride) % 100 == 0).to(torch.uint8), reward=ids.to(torch.float32))
+            rb.extend(torch.randint(0, 256, (n, fh, fw, fc), dtype=torch.uint8, device=dev, generator=g), **meta)
     else:
         from blendtorch.btt.gpu import DeviceLoader
         with btt.BlenderLauncher(producer='cubesim', num_instances=8, named_sockets=['DATA'], proto='ipc',
@@ -69,6 +161,9 @@ def main():
     fill_s = time.perf_counter() - t0
     crop = None if a.crop is None else ops.Crop(tuple(a.crop), mirror=a.mirror, pad=a.pad)
     cfg = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, dtype=a.dtype, crop=crop)
+    if a.stack:
+        return bench_stack(a, rb, cfg, fill_s)
+
     def legacy():
         idx = torch.randint(0, len(rb), (a.batch,), device=dev)
         out = {'image': ops.decode_gather(rb.store, idx, cfg), 'index': idx}

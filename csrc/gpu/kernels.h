@@ -259,6 +259,65 @@ struct ReplayCropParams {
 hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                               hipStream_t stream);
 
+// Frame-stacked TRANSITIONS out of the frame-once store, in ONE launch: for
+// image b the last `stack` frames of an environment stacked along channels
+// (obs), the stack one step later (next_obs), and the metadata at both ends.
+// The store is filled in lockstep, `stride` frames per step (one per
+// environment), so the same environment's previous step of ring slot s is
+// (s - stride) mod capacity; `first` (u8 [capacity]) is non-zero where a frame
+// is the first observation after a reset.  With head the next slot to be
+// written, age(s) = (head - 1 - s) mod capacity; a slot is stored iff
+// age < size.  S = stride, k = stack, C the launch's Philox counter:
+//   * draw: candidate t < 16 takes word t & 3 of the Philox4x32-10 block
+//     with key r.seed and counter words (b, C, C >> 32, c3), c3 = 0 for t < 4,
+//     else 1 + (t >> 2) (the window blocks are 1 and 5):
+//       a = S + ((word * (size - S)) >> 32);  anchor = (head - 1 - a) mod capacity
+//       successor = (anchor + S) mod capacity;  valid iff first[successor] == 0
+//     The smallest valid t wins.  If none is valid the image keeps candidate
+//     15 with the anchor as its own successor and valid_out[b] = 0.
+//     r.index_in gives the anchors instead (reduced mod capacity): valid iff
+//     S <= age(anchor) < size and first[successor] == 0.
+//   * frame table e[b][0 .. k]: e[k] = successor, e[k - 1] = anchor, and for
+//     j = k - 2 .. 0: e[j] = e[j + 1] if first[e[j + 1]] != 0 or
+//     age(e[j + 1]) + S >= size (the episode's first, or the oldest stored,
+//     frame repeats), else (e[j + 1] - S) mod capacity.  Every slot lies in
+//     [0, capacity) whatever `first` holds: no byte outside the store is read.
+//   * windows: c.h == 0: the whole frame.  Else replay_sample_crop's, one per
+//     STACK: obs from Philox block c3 = 1, next_obs from block 5 (the obs
+//     window again with shared_window); fixed windows serve both.
+//     c.windows_in is not supported.
+//   * output [2, B, k * Cout, h, w] (NCHW only), out[0] = obs, out[1] =
+//     next_obs; channel f * Cout + c of side d is channel c of frame
+//     e[b][f + d], oldest first.  Values are replay_sample_crop's bit for bit.
+//   * metadata: r.meta_* rows of the anchor e[k - 1]; next_* rows of e[k].
+// head / size: by value, or read from state (device int64[2]: head, size) when
+// state != nullptr -- a captured graph then follows a growing store.  A device
+// state with size <= S gives valid = 0 everywhere.  r.counter as in
+// replay_sample: a device counter advances by B behind the launch when
+// anything was drawn.  r.count is ignored.
+// hipErrorInvalidValue before anything is launched: stack outside [1, 16],
+// B > kMaxReplayB, B * (stack + 1) > 8192, stride outside [1, capacity),
+// capacity > 2^31, by value size <= stride, size > capacity or head outside
+// [0, capacity), no `first`, a layout other than NCHW, and everything
+// replay_sample_crop refuses.
+struct ReplayStackParams {
+  int stack = 1, stride = 1;
+  int64_t capacity = 0;
+  int64_t head = 0, size = 0;
+  const int64_t* state = nullptr;
+  const uint8_t* first = nullptr;
+  int shared_window = 0;
+  int64_t* next_index_out = nullptr;   // nullable, int64 [B]
+  uint8_t* valid_out = nullptr;        // nullable, u8 [B]
+  int32_t* next_crop_out = nullptr;    // nullable, int32 [B * 3] (c.crop_out: the obs windows)
+  int nnext = 0;
+  const uint8_t* next_src[kMaxMeta] = {};
+  uint8_t* next_dst[kMaxMeta] = {};
+  int next_bytes[kMaxMeta] = {};
+};
+hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                               const ReplayStackParams& t, hipStream_t stream);
+
 // Per-pixel affine colour transform on the MFMA units:
 //   out[b, c, y, x] = sum_k M[c][k] * lut[k][in[b, y, x, k]] + bias[c]
 // for RGBA u8 HWC input (Cin = 4), f32 NCHW output with Cout <= 4 channels;

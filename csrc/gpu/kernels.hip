@@ -1681,8 +1681,9 @@ __device__ __forceinline__ int64_t replay_frame(const ReplayParams& r, uint64_t 
 // image b's window, packed.  Given windows are clamped into the legal range
 // (the caller validated them; the clamp keeps every read inside the frame
 // whatever the tensor holds).
+// c3: the Philox block drawn from (1; the transitions' next stack takes 5).
 __device__ __forceinline__ uint32_t replay_window(const DecodeParams& p, const ReplayCropParams& c, uint64_t ctr,
-                                                  int b) {
+                                                  int b, uint32_t c3 = 1u) {
   int y0, x0, m = 0;
   if (c.windows_in) {
     y0 = clampi(c.windows_in[3 * b], -c.pad, p.H + c.pad - c.h);
@@ -1692,7 +1693,7 @@ __device__ __forceinline__ uint32_t replay_window(const DecodeParams& p, const R
     y0 = c.y0, x0 = c.x0;
   } else {
     uint32_t o[4];
-    philox_block(c.window_key, ctr, uint32_t(b), 1u, o);
+    philox_block(c.window_key, ctr, uint32_t(b), c3, o);
     y0 = int(__umulhi(o[0], c.ny)) - c.pad;
     x0 = int(__umulhi(o[1], c.nx)) * c.x_align - c.pad;
     m = (o[2] >> 8) < c.mirror_threshold;
@@ -1934,6 +1935,347 @@ hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, cons
   }
   // a device counter moves on when this launch drew from it: indices, or windows
   const bool drew = !r.index_in || (c.mode == kCropRandom && !c.windows_in);
+  if (e != hipSuccess || !r.counter || !drew) return e;
+  replay_advance_kernel<<<1, 1, 0, stream>>>(r.counter, p.B);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// frame-stacked transitions (kernels.h: replay_sample_stack)
+// ---------------------------------------------------------------------------
+// replay_crop_vec_kernel's body over 2 * B * k VIRTUAL images of Cout planes:
+// virtual image v = (d * B + b) * k + f is frame e[b][f + d] through window
+// win[d * B + b], and lands at v * Cout * h * w of the dense output -- which is
+// [2, B, k * Cout, h, w].  The block prologue builds the frame table and the
+// windows in dynamic LDS: 4 * (B * (k + 1) + 2 B) bytes.
+// Measured against the plain cropped sample of the same 2 B k images
+// (profiles/r14/replay_stack.md; 640x480 RGBA, pad 4, k = 3, fp32): batch 64
+// 340 against 334 us, batch 8 58.3 against 48.9 us -- the prologue's two
+// dependent flag loads (candidates, then the walk back) are paid by each of
+// the 8192 blocks, which at batch 8 have little else to do.  A one-block
+// table kernel in front would take them out of the blocks; it is not built.
+namespace {
+
+// s in [-cap, 2 cap) -> [0, cap)
+__device__ __forceinline__ int64_t ring_wrap(int64_t s, int64_t cap) { return s < 0 ? s + cap : (s >= cap ? s - cap : s); }
+
+// Fills tbl [B][k + 1] and win [2][B] (block 0 also the outputs); the caller
+// syncs.  The `first` flags are loaded in groups whose addresses do not
+// depend on each other: the four candidates of a Philox block, then the
+// slots the walk back may stop at; only the stop position follows them.
+__device__ __forceinline__ void stack_table(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                                            const ReplayStackParams& t, uint64_t ctr, uint32_t* tbl, uint32_t* win) {
+  const int k = t.stack, S = t.stride, B = p.B;
+  const int64_t cap = t.capacity;
+  // a device state was not seen by the host: reduced into the ring
+  int64_t head = t.state ? t.state[0] : t.head, size = t.state ? t.state[1] : t.size;
+  head = head < 0 ? 0 : (head >= cap ? cap - 1 : head);
+  size = size < 0 ? 0 : (size > cap ? cap : size);
+  const bool filled = size > S;
+  const uint32_t range = filled ? uint32_t(size - S) : 0u;
+  for (int b = threadIdx.x; b < B; b += kBlock) {
+    int64_t anchor = 0, succ = 0;
+    bool valid = false;
+    if (r.index_in) {
+      anchor = r.index_in[b] % cap;
+      if (anchor < 0) anchor += cap;
+      succ = ring_wrap(anchor + S, cap);
+      const int64_t age = ring_wrap(head - 1 - anchor, cap);
+      valid = filled && age >= S && age < size && t.first[succ] == 0;
+    } else {
+      for (int blk = 0; blk < 4 && !valid; ++blk) {
+        uint32_t o[4];
+        philox_block(r.seed, ctr, uint32_t(b), blk ? uint32_t(blk + 1) : 0u, o);
+        int64_t s[4], n[4];
+        uint8_t f[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          s[u] = ring_wrap(head - 1 - (int64_t(S) + __umulhi(o[u], range)), cap);
+          n[u] = ring_wrap(s[u] + S, cap);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f[u] = t.first[n[u]];
+        anchor = s[3];   // none valid: the block's last candidate
+#pragma unroll
+        for (int u = 3; u >= 0; --u)
+          if (f[u] == 0) anchor = s[u], succ = n[u], valid = true;
+      }
+      valid = valid && filled;
+    }
+    if (!valid) succ = anchor;
+    uint32_t* e = tbl + b * (k + 1);
+    e[k] = uint32_t(succ), e[k - 1] = uint32_t(anchor);
+    // walk back: slot c_m = anchor - m S, m < k - 1, stops the walk when it is
+    // a first frame or the oldest stored one; stopping is final, so the flags
+    // of all c_m are read at once (indices past k - 2 repeat the last)
+    uint32_t stop = 0;
+    int64_t s = anchor;
+    for (int m0 = 0; m0 < k - 1; m0 += 4) {
+      int64_t a[4];
+      uint8_t f[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        a[u] = s;
+        if (m0 + u < k - 2) s = ring_wrap(s - S, cap);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f[u] = t.first[a[u]];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (f[u] != 0) stop |= 1u << (m0 + u < k - 2 ? m0 + u : k - 2);
+    }
+    const int64_t age0 = ring_wrap(head - 1 - anchor, cap);
+    int mstop = k - 1;
+    for (int m = k - 2; m >= 0; --m)
+      if (((stop >> m) & 1u) || age0 + int64_t(m + 1) * S >= size) mstop = m;
+    s = anchor;
+    for (int m = 1; m <= k - 1; ++m) {
+      if (m <= mstop) s = ring_wrap(s - S, cap);
+      e[k - 1 - m] = uint32_t(s);
+    }
+    const uint32_t w0 = replay_window(p, c, ctr, b, 1u);
+    const uint32_t w1 = t.shared_window ? w0 : replay_window(p, c, ctr, b, 5u);
+    win[b] = w0, win[B + b] = w1;
+    if (blockIdx.x == 0) {
+      if (r.index_out) r.index_out[b] = anchor;
+      if (t.next_index_out) t.next_index_out[b] = succ;
+      if (t.valid_out) t.valid_out[b] = valid;
+      if (c.crop_out) {
+        c.crop_out[3 * b] = int(w0 & 0x7FFFu) - c.pad;
+        c.crop_out[3 * b + 1] = int((w0 >> 15) & 0x7FFFu) - c.pad;
+        c.crop_out[3 * b + 2] = int(w0 >> 31);
+      }
+      if (t.next_crop_out) {
+        t.next_crop_out[3 * b] = int(w1 & 0x7FFFu) - c.pad;
+        t.next_crop_out[3 * b + 1] = int((w1 >> 15) & 0x7FFFu) - c.pad;
+        t.next_crop_out[3 * b + 2] = int(w1 >> 31);
+      }
+    }
+  }
+}
+
+// metadata unit m of n columns gathered at table column `col` (replay_meta's units)
+__device__ __forceinline__ void stack_meta_cols(int n, const uint8_t* const* src, uint8_t* const* dst, const int* bytes,
+                                                const uint32_t* tbl, int k1, int col, int B, int64_t m) {
+  for (int q = 0; q < n; ++q) {
+    const int nb = bytes[q];
+    const int w = (nb % 4 == 0) ? 4 : 1;
+    const int64_t per = nb / w, units = per * B;
+    if (m < units) {
+      const int b = int(m / per);
+      const int64_t j = (m - int64_t(b) * per) * w;
+      const uint8_t* s = src[q] + int64_t(tbl[b * k1 + col]) * nb + j;
+      uint8_t* d = dst[q] + int64_t(b) * nb + j;
+      if (w == 4) *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
+      else *d = *s;
+      return;
+    }
+    m -= units;
+  }
+}
+
+// anchor columns (r.meta_*, from e[k - 1]) first, then the next columns (from e[k])
+__device__ __forceinline__ void stack_meta(const ReplayParams& r, const ReplayStackParams& t, const uint32_t* tbl, int B,
+                                           int64_t anchor_units, int64_t m) {
+  if (m < anchor_units) stack_meta_cols(r.nmeta, r.meta_src, r.meta_dst, r.meta_bytes, tbl, t.stack + 1, t.stack - 1, B, m);
+  else stack_meta_cols(t.nnext, t.next_src, t.next_dst, t.next_bytes, tbl, t.stack + 1, t.stack, B, m - anchor_units);
+}
+
+// virtual image v -> its frame slot and packed window
+__device__ __forceinline__ void stack_resolve(const uint32_t* tbl, const uint32_t* win, int B, int k, uint32_t v,
+                                              uint32_t& slot, uint32_t& w) {
+  const uint32_t Bk = uint32_t(B) * uint32_t(k);
+  const uint32_t d = v >= Bk ? 1u : 0u;
+  const uint32_t rem = v - d * Bk;
+  const uint32_t b = rem / uint32_t(k), f = rem - b * uint32_t(k);
+  slot = tbl[b * uint32_t(k + 1) + f + d];
+  w = win[d * uint32_t(B) + b];
+}
+
+// TBL / NT: replay_crop_vec_kernel's choices, inherited
+template <int PPT, int CIN, int OUTT, int TBL, bool NT = false>
+__global__ __launch_bounds__(kBlock) void replay_stack_vec_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
+                                                                  ReplayStackParams t, int64_t meta_units,
+                                                                  int64_t anchor_units) {
+  __shared__ uint32_t tab[kTabWords];
+  extern __shared__ uint32_t stack_lds[];
+  uint32_t* tbl = stack_lds;
+  uint32_t* win = stack_lds + p.B * (t.stack + 1);
+  const int64_t hw = int64_t(c.h) * c.w;
+  const int64_t groups_per_img = hw / PPT;
+  const int64_t groups = groups_per_img * 2 * p.B * t.stack;
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cm[q] = p.cmap[q];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  const bool small = groups + meta_units + stride < (int64_t(1) << 31);
+  const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  stack_table(p, r, c, t, ctr, tbl, win);
+  __syncthreads();
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < groups + meta_units; g += stride) {
+    if (g >= groups) {
+      stack_meta(r, t, tbl, p.B, anchor_units, g - groups);
+      continue;
+    }
+    Group gr;
+    int i, j;
+    split_group<PPT>(g, groups_per_img, c.w, small, gr.b, gr.q, i, j);
+    uint32_t slot, w;
+    stack_resolve(tbl, win, p.B, t.stack, uint32_t(gr.b), slot, w);
+    Pixels<PPT, CIN> px;
+    if (load_crop_group<PPT, CIN>(p, r, c, int64_t(slot), w, i, j, px)) reverse_pixels<PPT, CIN>(px);
+    emit<PPT, CIN, OUTT, NCHW, TBL, NT>(p, xf, cm, cout, hw, gr, px);
+  }
+}
+
+// any window size / alignment / channel count: one window pixel per lane
+template <int OUTT>
+__global__ __launch_bounds__(kBlock) void replay_stack_scalar_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
+                                                                     ReplayStackParams t, int64_t meta_units,
+                                                                     int64_t anchor_units) {
+  __shared__ uint32_t tab[kTabWords];
+  extern __shared__ uint32_t stack_lds[];
+  uint32_t* tbl = stack_lds;
+  uint32_t* wins = stack_lds + p.B * (t.stack + 1);
+  const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  stack_table(p, r, c, t, ctr, tbl, wins);
+  __syncthreads();
+  const int64_t hw = int64_t(c.h) * c.w;
+  const int64_t total = hw * 2 * p.B * t.stack;
+  const int64_t ie = hw * p.Cout;
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total + meta_units; g += int64_t(gridDim.x) * kBlock) {
+    if (g >= total) {
+      stack_meta(r, t, tbl, p.B, anchor_units, g - total);
+      continue;
+    }
+    const int64_t v = g / hw;
+    const int64_t q = g - v * hw;
+    const int i = int(q / c.w), j = int(q - int64_t(i) * c.w);
+    uint32_t slot, win;
+    stack_resolve(tbl, wins, p.B, t.stack, uint32_t(v), slot, win);
+    const int y0 = int(win & 0x7FFFu) - c.pad, x0 = int((win >> 15) & 0x7FFFu) - c.pad;
+    const int y = clampi(y0 + i, 0, p.H - 1);
+    const int sy = p.flip_all ? p.H - 1 - y : y;
+    const int x = clampi(x0 + ((win >> 31) ? c.w - 1 - j : j), 0, p.W - 1);
+    const uint8_t* s = p.src + int64_t(slot) * r.frame_bytes + (int64_t(sy) * p.W + x) * p.Cin;
+    for (int ch = 0; ch < p.Cout; ++ch) {
+      const float val = xf_value(xf, ch, s[p.cmap[ch]]);
+      const int64_t off = v * ie + int64_t(ch) * hw + q;
+      if constexpr (OUTT == OUT_F32) reinterpret_cast<float*>(p.dst)[off] = val;
+      else if constexpr (OUTT == OUT_BF16) reinterpret_cast<uint16_t*>(p.dst)[off] = f2bf(val);
+      else if constexpr (OUTT == OUT_F16) reinterpret_cast<uint16_t*>(p.dst)[off] = f2h(val);
+      else reinterpret_cast<uint8_t*>(p.dst)[off] = uint8_t(val);
+    }
+  }
+}
+
+template <int PPT, int CIN, int OUTT>
+void launch_replay_stack_vec(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                             const ReplayStackParams& t, int64_t meta_units, int64_t anchor_units, int grid, size_t lds,
+                             hipStream_t s) {
+  if constexpr (OUTT == OUT_F32) {
+    if (p.xf_table_only) {
+      // non-temporal stores as in launch_replay_crop_vec (BT_REPLAY_CROP_NT=0: plain stores)
+      static const bool nt = !(std::getenv("BT_REPLAY_CROP_NT") && std::getenv("BT_REPLAY_CROP_NT")[0] == '0');
+      if (nt) replay_stack_vec_kernel<PPT, CIN, OUTT, 1, true><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+      else replay_stack_vec_kernel<PPT, CIN, OUTT, 1><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+      return;
+    }
+  }
+  if (p.xf_table_only) replay_stack_vec_kernel<PPT, CIN, OUTT, 1><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+  else replay_stack_vec_kernel<PPT, CIN, OUTT, 0><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+}
+
+template <int OUTT>
+hipError_t launch_replay_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
+                               const ReplayStackParams& t, int64_t meta_units, int64_t anchor_units, hipStream_t s) {
+  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  const size_t lds = sizeof(uint32_t) * (size_t(p.B) * size_t(t.stack + 1) + 2 * size_t(p.B));
+  const int64_t pixels = int64_t(2) * p.B * t.stack * c.h * c.w;
+  // launch_replay_crop's vector conditions
+  const bool vec = (c.w % PPT) == 0 && (p.W % 4) == 0 && r.frame_bytes % 16 == 0 && (p.Cin == 3 || p.Cin == 4) &&
+                   (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0 &&
+                   (int64_t(c.h) * c.w * p.Cout * ELEM) % 16 == 0;
+  if (vec) {
+    const int grid = grid_for(pixels / PPT + meta_units, p.max_grid);
+    if (p.Cin == 4) launch_replay_stack_vec<PPT, 4, OUTT>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
+    else launch_replay_stack_vec<PPT, 3, OUTT>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
+  } else {
+    replay_stack_scalar_kernel<OUTT><<<grid_for(pixels + meta_units, p.max_grid), kBlock, lds, s>>>(p, r, c, t, meta_units,
+                                                                                                   anchor_units);
+  }
+  return hipGetLastError();
+}
+
+// units of n metadata columns for B images; false: a column is malformed
+bool meta_cols_units(int n, const uint8_t* const* src, uint8_t* const* dst, const int* bytes, int B, int64_t& units) {
+  units = 0;
+  if (n < 0 || n > kMaxMeta) return false;
+  for (int q = 0; q < n; ++q) {
+    const int nb = bytes[q];
+    if (nb <= 0 || !src[q] || !dst[q]) return false;
+    if (nb % 4 == 0 && ((reinterpret_cast<uintptr_t>(src[q]) | reinterpret_cast<uintptr_t>(dst[q])) % 4)) return false;
+    units += int64_t(B) * (nb % 4 == 0 ? nb / 4 : nb);
+  }
+  return true;
+}
+
+}  // namespace
+
+hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c0,
+                               const ReplayStackParams& t, hipStream_t stream) {
+  // every condition is checked here, before anything is launched
+  if (p.B < 0 || p.B > kMaxReplayB || p.H <= 0 || p.W <= 0 || p.Cin < 1 || p.Cin > 4 || p.Cout < 1 || p.Cout > 4 ||
+      !p.src || !p.dst || !p.lut || p.nsrcs || p.ndsts || p.src_offsets || p.flip ||
+      r.frame_bytes != int64_t(p.H) * p.W * p.Cin || p.layout != NCHW)
+    return hipErrorInvalidValue;
+  if (t.stack < 1 || t.stack > 16 || int64_t(p.B) * (t.stack + 1) > 8192) return hipErrorInvalidValue;
+  if (t.capacity < 2 || t.capacity > (int64_t(1) << 31) || t.stride < 1 || t.stride >= t.capacity || !t.first)
+    return hipErrorInvalidValue;
+  if (!t.state && (t.size <= t.stride || t.size > t.capacity || t.head < 0 || t.head >= t.capacity))
+    return hipErrorInvalidValue;
+  ReplayCropParams c = c0;
+  if (c.h == 0 && c.w == 0) {   // no crop: the whole frame at (0, 0)
+    c = ReplayCropParams();
+    c.h = p.H, c.w = p.W, c.mode = kCropFixed;
+    if (p.H > 32767 || p.W > 32767) return hipErrorInvalidValue;
+  }
+  if (c.windows_in) return hipErrorInvalidValue;
+  if (c.h <= 0 || c.w <= 0 || c.pad < 0 || c.pad > 16383 || p.H + 2 * c.pad > 32767 || p.W + 2 * c.pad > 32767 ||
+      c.h > p.H + 2 * c.pad || c.w > p.W + 2 * c.pad)
+    return hipErrorInvalidValue;
+  if (c.x_align != 1 && c.x_align != 4 && c.x_align != 16) return hipErrorInvalidValue;
+  if (c.mode != kCropRandom && c.mode != kCropFixed) return hipErrorInvalidValue;
+  if (c.mirror_threshold > (1u << 24)) return hipErrorInvalidValue;
+  if (c.pad != 0 && (c.x_align != 1 || c.mode != kCropRandom)) return hipErrorInvalidValue;
+  if (c.mode == kCropFixed && (c.y0 < 0 || c.x0 < 0 || c.y0 + c.h > p.H || c.x0 + c.w > p.W)) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(c.crop_out) | reinterpret_cast<uintptr_t>(t.next_crop_out)) % 4) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(r.index_in) | reinterpret_cast<uintptr_t>(r.index_out) |
+       reinterpret_cast<uintptr_t>(t.next_index_out) | reinterpret_cast<uintptr_t>(t.state)) % 8)
+    return hipErrorInvalidValue;
+  for (int q = 0; q < p.Cout; ++q)
+    if (p.cmap[q] < 0 || p.cmap[q] >= p.Cin) return hipErrorInvalidValue;
+  int64_t anchor_units = 0, next_units = 0;
+  if (!meta_cols_units(r.nmeta, r.meta_src, r.meta_dst, r.meta_bytes, p.B, anchor_units) ||
+      !meta_cols_units(t.nnext, t.next_src, t.next_dst, t.next_bytes, p.B, next_units))
+    return hipErrorInvalidValue;
+  if (p.B == 0) return hipSuccess;
+  c.ny = uint32_t(p.H + 2 * c.pad - c.h + 1);
+  c.nx = uint32_t((p.W + 2 * c.pad - c.w) / c.x_align + 1);
+  const int64_t meta_units = anchor_units + next_units;
+  hipError_t e = hipErrorInvalidValue;
+  switch (p.out_dtype) {
+    case OUT_F32: e = launch_replay_stack<OUT_F32>(p, r, c, t, meta_units, anchor_units, stream); break;
+    case OUT_BF16: e = launch_replay_stack<OUT_BF16>(p, r, c, t, meta_units, anchor_units, stream); break;
+    case OUT_F16: e = launch_replay_stack<OUT_F16>(p, r, c, t, meta_units, anchor_units, stream); break;
+    case OUT_U8: e = launch_replay_stack<OUT_U8>(p, r, c, t, meta_units, anchor_units, stream); break;
+  }
+  // a device counter moves on when this launch drew from it: anchors, or windows
+  const bool drew = !r.index_in || c.mode == kCropRandom;
   if (e != hipSuccess || !r.counter || !drew) return e;
   replay_advance_kernel<<<1, 1, 0, stream>>>(r.counter, p.B);
   return hipGetLastError();

@@ -452,6 +452,97 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("x_align") = 1, py::arg("window_key") = uint64_t(0), py::arg("windows_in") = uintptr_t(0),
         py::arg("crop_out") = uintptr_t(0));
 
+  // frame-stacked transitions (kernels.h: replay_sample_stack); crop_size empty: whole frames
+  m.def("replay_transitions",
+        [](uintptr_t store, int64_t capacity, int64_t head, int64_t size, uintptr_t state, uintptr_t first, int stack,
+           int stride, uintptr_t dst, uintptr_t lut, int B, int H, int W, int Cin, int Cout, std::vector<int> cmap,
+           int flip_all, int out_dtype, int layout, uint64_t seed, uintptr_t counter, uint64_t ctr_value,
+           uintptr_t index_in, uintptr_t index_out, uintptr_t next_index_out, uintptr_t valid_out,
+           std::vector<uintptr_t> meta_src, std::vector<uintptr_t> meta_dst, std::vector<int> meta_bytes,
+           std::vector<uintptr_t> next_src, std::vector<uintptr_t> next_dst, std::vector<int> next_bytes,
+           uintptr_t stream, int xf_table_only, int max_grid, std::vector<int> crop_size, std::string crop_mode,
+           std::vector<int> crop_origin, int crop_pad, double mirror, int x_align, uint64_t window_key,
+           int shared_window, uintptr_t crop_out, uintptr_t next_crop_out) {
+          DecodeParams p;
+          p.xf_table_only = xf_table_only;
+          p.max_grid = max_grid;
+          p.src = ptr<const uint8_t>(store);
+          p.dst = ptr<void>(dst);
+          p.lut = ptr<const float>(lut);
+          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+          fill_cmap(p.cmap, cmap);
+          p.flip_all = flip_all;
+          p.out_dtype = out_dtype;
+          p.layout = layout;
+          ReplayParams r;
+          r.frame_bytes = int64_t(H) * W * Cin;
+          r.seed = seed;
+          r.counter = ptr<uint64_t>(counter);
+          r.ctr_value = ctr_value;
+          r.index_in = ptr<const int64_t>(index_in);
+          r.index_out = ptr<int64_t>(index_out);
+          ReplayStackParams t;
+          t.stack = stack, t.stride = stride;
+          t.capacity = capacity, t.head = head, t.size = size;
+          t.state = ptr<const int64_t>(state);
+          t.first = ptr<const uint8_t>(first);
+          t.shared_window = shared_window;
+          t.next_index_out = ptr<int64_t>(next_index_out);
+          t.valid_out = ptr<uint8_t>(valid_out);
+          t.next_crop_out = ptr<int32_t>(next_crop_out);
+          if (meta_src.size() != meta_dst.size() || meta_src.size() != meta_bytes.size() ||
+              meta_src.size() > size_t(kMaxMeta) || next_src.size() != next_dst.size() ||
+              next_src.size() != next_bytes.size() || next_src.size() > size_t(kMaxMeta))
+            throw std::invalid_argument("replay_transitions: metadata columns mismatch or > kMaxMeta");
+          r.nmeta = int(meta_src.size());
+          for (int k = 0; k < r.nmeta; ++k) {
+            r.meta_src[k] = ptr<const uint8_t>(meta_src[size_t(k)]);
+            r.meta_dst[k] = ptr<uint8_t>(meta_dst[size_t(k)]);
+            r.meta_bytes[k] = meta_bytes[size_t(k)];
+          }
+          t.nnext = int(next_src.size());
+          for (int k = 0; k < t.nnext; ++k) {
+            t.next_src[k] = ptr<const uint8_t>(next_src[size_t(k)]);
+            t.next_dst[k] = ptr<uint8_t>(next_dst[size_t(k)]);
+            t.next_bytes[k] = next_bytes[size_t(k)];
+          }
+          ReplayCropParams c;
+          if (!crop_size.empty()) {
+            if (crop_size.size() != 2 || (!crop_origin.empty() && crop_origin.size() != 2))
+              throw std::invalid_argument("replay_transitions: crop_size is (h, w) and crop_origin (y0, x0)");
+            if (!(mirror >= 0.0 && mirror <= 1.0))
+              throw std::invalid_argument("replay_transitions: mirror is a probability");
+            c.h = crop_size[0], c.w = crop_size[1], c.pad = crop_pad;
+            if (c.h == 0 || c.w == 0) c.h = c.w = -1;   // an empty window is refused, not taken for "no crop"
+            c.x_align = x_align;
+            if (!crop_origin.empty()) {
+              c.mode = kCropFixed, c.y0 = crop_origin[0], c.x0 = crop_origin[1];
+            } else if (crop_mode == "center") {
+              c.mode = kCropFixed;
+              c.y0 = (H - c.h) / 2;
+              c.x0 = x_align > 0 ? (W - c.w) / 2 / x_align * x_align : 0;
+            } else if (crop_mode == "random") {
+              c.mode = kCropRandom;
+            } else {
+              throw std::invalid_argument("replay_transitions: crop_mode is 'random' or 'center'");
+            }
+            c.mirror_threshold = uint32_t(mirror * 16777216.0);
+            c.window_key = window_key;
+            c.crop_out = ptr<int32_t>(crop_out);
+          }
+          check(replay_sample_stack(p, r, c, t, stream_of(stream)), "replay_sample_stack");
+        },
+        py::arg("store"), py::arg("capacity"), py::arg("head"), py::arg("size"), py::arg("state"), py::arg("first"),
+        py::arg("stack"), py::arg("stride"), py::arg("dst"), py::arg("lut"), py::arg("B"), py::arg("H"), py::arg("W"),
+        py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"), py::arg("out_dtype"), py::arg("layout"),
+        py::arg("seed"), py::arg("counter"), py::arg("ctr_value"), py::arg("index_in"), py::arg("index_out"),
+        py::arg("next_index_out"), py::arg("valid_out"), py::arg("meta_src"), py::arg("meta_dst"), py::arg("meta_bytes"),
+        py::arg("next_src"), py::arg("next_dst"), py::arg("next_bytes"), py::arg("stream"),
+        py::arg("xf_table_only") = 0, py::arg("max_grid") = 0, py::arg("crop_size") = std::vector<int>(),
+        py::arg("crop_mode") = "random", py::arg("crop_origin") = std::vector<int>(), py::arg("crop_pad") = 0,
+        py::arg("mirror") = 0.0, py::arg("x_align") = 1, py::arg("window_key") = uint64_t(0),
+        py::arg("shared_window") = 0, py::arg("crop_out") = uintptr_t(0), py::arg("next_crop_out") = uintptr_t(0));
+
   m.def("multi_cast",
         [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst, std::vector<int64_t> numel, int mode,
            uintptr_t stream) {

@@ -25,6 +25,10 @@ epoch after the first then runs at HBM speed without touching the host:
   crop + mirror, or with ``Crop(frame_size, pad=4)`` the random shift of
   DrQ / RAD (replicate padding).  The batch reports its windows as
   ``batch['crop']``; a graphed sampler draws fresh ones on every replay.
+* ``sample_transitions(B, decode, stack=k, stride=S)``: frame-stacked
+  transitions for pixel-based RL (``obs``, ``next_obs``, the metadata at both
+  ends) assembled by the sample kernel from frames stored once; episode
+  starts come from a one-byte ``first`` metadata column.
 
 On a CPU device the same API runs with the fp32 reference ops (tests, hosts
 without a GPU). On a GPU device the HIP kernels are required and fail loudly
@@ -80,6 +84,8 @@ class DeviceReplayBuffer:
         # device counter the captured graph advances itself)
         self.seed = int(torch.initial_seed() if seed is None else seed) & (2 ** 64 - 1)
         self._ctr = 0
+        # device int64 (head, size) for graphed transition samplers; None until one exists
+        self._state: Optional[torch.Tensor] = None
         if self.device.type == 'cuda':
             ops.hip_ext()   # fail loudly here, not at the first sample()
 
@@ -130,6 +136,8 @@ class DeviceReplayBuffer:
             self._next = (self._next + k) % self.capacity
             pos += k
         self._size = min(self.capacity, self._size + n)
+        if self._state is not None:   # a graphed transition sampler reads the ring state from the device
+            self._state.copy_(torch.tensor([self._next, self._size], dtype=torch.int64))
         return self
 
     def fill_from(self, batches, max_items: int):
@@ -378,6 +386,151 @@ class DeviceReplayBuffer:
             graph.replay()
             return out
         replay.graph = graph
+        return replay
+
+    # -- frame-stacked transitions ------------------------------------------------
+    def _transitions(self, B, idx, decode, stack, stride, first_key, next_keys, shared_window, _counter):
+        if self._size == 0:
+            raise IndexError('empty replay buffer')
+        ops._transition_cfg(decode, 'DeviceReplayBuffer transitions')
+        first = self.meta.get(first_key)
+        if first is None or first.dim() != 1 or first.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f'transitions need a uint8 / bool [capacity] metadata column {first_key!r} '
+                             '(episode starts): extend(frames, ..., %s=flags)' % first_key)
+        next_keys = tuple(next_keys)
+        for k in next_keys:
+            if k not in self.meta:
+                raise ValueError(f'next_keys: no metadata column {k!r}')
+        stack, stride = int(stack), int(stride)
+        if not 1 <= stack <= ops.MAX_STACK or B * (stack + 1) > ops.MAX_STACK_TABLE:
+            raise ValueError(f'stack must lie in [1, {ops.MAX_STACK}] with batch * (stack + 1) <= {ops.MAX_STACK_TABLE}')
+        if not 1 <= stride < self.capacity:
+            raise ValueError('stride must lie in [1, capacity)')
+        if self._size <= stride:
+            raise ValueError(f'transitions need more than stride = {stride} stored frames: {self._size}')
+        crop = decode.crop
+        ctr = _counter
+        if ctr is None:
+            ctr = self._ctr
+            if idx is None or (crop is not None and crop.kind == 'random'):   # something is drawn
+                self._ctr += B
+        if self.device.type == 'cuda':
+            if not self.store.is_contiguous():
+                raise ValueError('transitions need a contiguous store')
+            out, info = ops.replay_transitions(
+                self.store, self._next, self._size, B, decode, stack=stack, stride=stride, first=first, seed=self.seed,
+                counter=ctr, index=idx, meta=self.meta, next_meta={k: self.meta[k] for k in next_keys},
+                shared_window=shared_window, state=self._state if isinstance(ctr, torch.Tensor) else None)
+            batch = {'obs': out[0], 'next_obs': out[1], **info['meta']}
+            batch.update({'next_' + k: v for k, v in info['next_meta'].items()})
+            batch.update(index=info['index'], next_index=info['next_index'], valid=info['valid'])
+            if crop is not None:
+                batch.update(crop=info['crop'], next_crop=info['next_crop'])
+            return batch
+        # the reference path: the numpy references of the kernel's draws + reference_decode
+        ring = (self._next, self._size, self.capacity, stride, stack, first.numpy())
+        if idx is None:
+            anchor, succ, table, valid = ops.philox_transitions(self.seed, ctr, B, *ring)
+        else:
+            anchor, succ, table, valid = ops.given_transitions(idx.cpu().numpy(), *ring)
+        H, W = self.frame_shape[:2]
+        wins = None
+        if crop is not None:
+            crop.check_frame(H, W)
+            wins = ops.transition_windows(crop, H, W, B, seed=self.seed, counter=ctr, shared_window=shared_window)
+        sides = []
+        for d in (0, 1):
+            planes = [ops.reference_decode(self.store.index_select(0, torch.from_numpy(table[:, f + d])), decode,
+                                           crop=None if wins is None else wins[d]) for f in range(stack)]
+            sides.append(torch.cat(planes, dim=1))
+        anchor, succ = torch.from_numpy(anchor), torch.from_numpy(succ)
+        batch = {'obs': sides[0], 'next_obs': sides[1]}
+        batch.update({k: v.index_select(0, anchor) for k, v in self.meta.items()})
+        batch.update({'next_' + k: self.meta[k].index_select(0, succ) for k in next_keys})
+        batch.update(index=anchor, next_index=succ, valid=torch.from_numpy(valid))
+        if wins is not None:
+            batch.update(crop=torch.from_numpy(wins[0].copy()), next_crop=torch.from_numpy(wins[1].copy()))
+        return batch
+
+    def sample_transitions(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
+                           stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
+                           _counter=None):
+        """A batch of frame-stacked transitions out of the frame-once store.
+
+        Storage convention (nothing about ``extend`` changes): an RL loop
+        appends ``stride`` frames per environment step, one per environment
+        and always in the same order (``stride = len(vec_env)``, 1 for a single
+        environment), so the same environment's previous step of ring slot s
+        is ``(s - stride) mod capacity``.  The one-byte metadata column
+        ``first_key`` (uint8 / bool) is non-zero where a frame is the first
+        observation after a reset; terminal observations are stored like any
+        other frame, and the frame after one is a ``first`` frame.
+
+        Returns ``obs`` and ``next_obs`` (``[B, stack * Cout, h, w]``, NCHW:
+        the last ``stack`` frames ending at the anchor, resp. one step later,
+        oldest first along channels; a stack that reaches back over an
+        episode start, or past the oldest stored frame, repeats that frame),
+        every metadata column at the anchor (action, reward, done ...),
+        ``'next_' + key`` at the successor for ``next_keys``, ``index`` /
+        ``next_index`` (the anchor's and the successor's slot) and ``valid``.
+        No transition crosses a reset: an anchor whose successor is a
+        ``first`` frame is redrawn, up to 16 times (``ops.philox_transitions``);
+        ``valid`` is False for an image that found none (its ``next_index`` is
+        its ``index``): mask it out of the loss.
+
+        With ``decode.crop`` one window serves all frames of a stack and the
+        two stacks take independent windows (``crop`` / ``next_crop``), as DrQ
+        augments them, unless ``shared_window``.  On a GPU all of it is ONE
+        launch (``ops.replay_transitions``); a CPU buffer with the same seed
+        and call sequence returns the same batches.  Colour-kernel, resize
+        and NHWC configs raise ``ValueError`` (NHWC: channel-stacked
+        channels-last output needs another store pattern)."""
+        return self._transitions(int(batch_size), None, decode, stack, stride, first_key, next_keys, shared_window,
+                                 _counter)
+
+    def gather_transitions(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
+                           stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
+                           _counter=None):
+        """:meth:`sample_transitions` at given anchors ``idx`` (slots).
+        ``valid`` is False where the anchor is among the newest ``stride``
+        frames, is not stored, or its successor is a ``first`` frame.  A random
+        crop draws its windows at the buffer's Philox counter."""
+        idx = idx.to(self.device, torch.int64).reshape(-1)
+        return self._transitions(int(idx.numel()), idx, decode, stack, stride, first_key, next_keys, shared_window,
+                                 _counter)
+
+    def graphed_transition_sampler(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
+                                   stride: int = 1, first_key: str = 'first', next_keys=(),
+                                   shared_window: bool = False, warmup: int = 3):
+        """:meth:`sample_transitions` captured once as a HIP graph.  The
+        Philox counter lives in device memory (as in :meth:`graphed_sampler`)
+        and so does the ring state: the kernel reads ``(head, size)`` from a
+        device tensor that ``extend`` refreshes once such a sampler exists, so
+        ONE capture serves a buffer that grows every environment step.  The
+        returned callable replays the graph and returns the same static
+        output dict every time."""
+        kw = dict(stack=stack, stride=stride, first_key=first_key, next_keys=next_keys, shared_window=shared_window)
+        if self.device.type != 'cuda':
+            return lambda: self.sample_transitions(batch_size, decode, **kw)
+        if self._state is None:
+            self._state = torch.tensor([self._next, self._size], dtype=torch.int64, device=self.device)
+        counter = torch.tensor([self._ctr], dtype=torch.int64, device=self.device)
+        self._ctr += 1 << 40          # disjoint from later eager draws
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self.sample_transitions(batch_size, decode, _counter=counter, **kw)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self.sample_transitions(batch_size, decode, _counter=counter, **kw)
+
+        def replay():
+            graph.replay()
+            return out
+        replay.graph = graph
+        replay.counter = counter
         return replay
 
     def batches(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), shuffle: bool = True,

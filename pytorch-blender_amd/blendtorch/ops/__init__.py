@@ -30,7 +30,7 @@ import numpy as np
 
 __all__ = [
     'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'ResizedCrop', 'resized_windows', 'resized_crop_points', 'philox_windows', 'replay_windows', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
-    'color4x4',
+    'color4x4', 'replay_transitions', 'philox_transitions', 'given_transitions', 'transition_windows',
     'project', 'adaptive_avg_pool_nhwc', 'AdaptiveAvgPool2d', 'batch_norm_leaky_relu', 'BatchNormLeakyReLU2d',
     'reference_decode', 'reference_color4x4', 'reference_project', 'reference_gamma',
 ]
@@ -1190,7 +1190,7 @@ def replay_windows(crop: Crop, H: int, W: int, B: int, seed: int = 0, counter: i
     return crop_windows(crop, H, W, B)
 
 
-def philox_windows(seed: int, counter: int, B: int, crop: Crop, H: int, W: int) -> np.ndarray:
+def philox_windows(seed: int, counter: int, B: int, crop: Crop, H: int, W: int, block: int = 1) -> np.ndarray:
     """The windows :func:`replay_sample` draws for a random ``crop`` (numpy
     reference), int32 [B, 3] of (y0, x0, mirrored), origin in frame
     coordinates (negative, or leaving the frame, with a ``pad``).  Image b
@@ -1202,14 +1202,17 @@ def philox_windows(seed: int, counter: int, B: int, crop: Crop, H: int, W: int) 
 
         y0 = -pad + ((o0 * (H + 2*pad - h + 1)) >> 32)
         x0 = -pad + ((o1 * ((W + 2*pad - w) // x_align + 1)) >> 32) * x_align
-        m  = (o2 >> 8) < int(mirror * 2**24)"""
+        m  = (o2 >> 8) < int(mirror * 2**24)
+
+    ``block``: the last counter word.  1 everywhere but for the next-observation
+    stack of :func:`replay_transitions`, which draws from block 5."""
     if crop.kind != 'random':
         raise ValueError("philox_windows: only mode 'random' draws its windows")
     crop.check_frame(H, W)
     h, w = crop.size
     pad, a = crop.pad, crop.x_align
     key = (int(seed) + crop.seed) & (2 ** 64 - 1)
-    o0, o1, o2, _ = _philox_blocks(key, int(counter) & (2 ** 64 - 1), B, 1)
+    o0, o1, o2, _ = _philox_blocks(key, int(counter) & (2 ** 64 - 1), B, int(block))
     out = np.zeros((B, 3), np.int32)
     s32 = np.uint64(32)
     out[:, 0] = ((o0 * np.uint64(H + 2 * pad - h + 1)) >> s32).astype(np.int64) - pad
@@ -1324,6 +1327,228 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
     if crop is not None:
         return out, idx_out, mout, crop_out
     return out, idx_out, mout
+
+
+# ---- frame-stacked transitions ----------------------------------------------------------------------------------
+# Storage convention (DeviceReplayBuffer.sample_transitions): frames are appended in lockstep, `stride` per
+# environment step, so the same environment's previous step of ring slot s is (s - stride) mod capacity; `first`
+# marks the first observation after a reset.  head: the next slot written; age(s) = (head - 1 - s) mod capacity;
+# a slot is stored iff age < size.
+
+MAX_STACK = 16            # kernels.h: replay_sample_stack
+MAX_STACK_TABLE = 8192    # B * (stack + 1)
+
+
+def _ring_args(head, size, capacity, stride, stack, first):
+    head, size, capacity, stride, stack = int(head), int(size), int(capacity), int(stride), int(stack)
+    if not 1 <= stack <= MAX_STACK:
+        raise ValueError(f'stack must lie in [1, {MAX_STACK}]')
+    if not 1 <= stride < capacity:
+        raise ValueError('stride must lie in [1, capacity)')
+    if not (stride < size <= capacity):
+        raise ValueError(f'transitions need more than stride = {stride} stored frames (and at most capacity): {size}')
+    if not 0 <= head < capacity:
+        raise ValueError('head must lie in [0, capacity)')
+    first = np.asarray(first).reshape(-1) != 0
+    if first.shape[0] != capacity:
+        raise ValueError(f'first must hold one flag per slot ({capacity})')
+    return head, size, capacity, stride, stack, first
+
+
+def _frame_table(anchor, succ, head, size, capacity, stride, stack, first):
+    """int64 [B, stack + 1]: e[k] the successor, e[k - 1] the anchor, then backwards one step at a time; the
+    walk stays on a ``first`` frame and on the oldest stored frame."""
+    k = stack
+    e = np.zeros((len(anchor), k + 1), np.int64)
+    e[:, k], e[:, k - 1] = succ, anchor
+    for j in range(k - 2, -1, -1):
+        nxt = e[:, j + 1]
+        stop = first[nxt] | ((head - 1 - nxt) % capacity + stride >= size)
+        e[:, j] = np.where(stop, nxt, (nxt - stride) % capacity)
+    return e
+
+
+def philox_transitions(seed: int, counter: int, B: int, head: int, size: int, capacity: int, stride: int, stack: int,
+                       first):
+    """The transitions :func:`replay_transitions` draws (numpy reference):
+    ``(anchors, successors, table, valid)`` -- int64 [B], int64 [B], int64
+    [B, stack + 1] and bool [B].
+
+    Image b tries up to 16 candidates.  Candidate t takes output word
+    ``t & 3`` of the Philox4x32-10 block with key ``seed`` and counter words
+    ``(b, counter & 0xffffffff, counter >> 32, c3)``, ``c3 = 0`` for t < 4
+    (word 0 is :func:`philox_indices`' word) and ``1 + (t >> 2)`` after (the
+    window blocks are 1 and 5)::
+
+        a = stride + ((word * (size - stride)) >> 32)     # age of the anchor: never among the newest `stride`
+        anchor = (head - 1 - a) % capacity
+        successor = (anchor + stride) % capacity
+
+    and is valid iff ``first[successor] == 0`` (a transition does not cross
+    a reset).  The smallest valid t wins; an image without one keeps candidate
+    15 with ``successor = anchor`` and ``valid = False``.  ``table[b]`` lists
+    the slots of the ``stack`` frames ending at the anchor, oldest first,
+    then the successor: walking back by ``stride`` from the anchor, the walk
+    stays where it is on a ``first`` frame (the episode's first frame
+    repeats) and on the oldest stored frame.  The observation stack is
+    ``table[:, :stack]``, the next one ``table[:, 1:]``."""
+    head, size, capacity, stride, stack, first = _ring_args(head, size, capacity, stride, stack, first)
+    anchor, succ = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    valid = np.zeros(B, bool)
+    s = anchor
+    for blk in range(4):
+        words = _philox_blocks(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), B, blk + 1 if blk else 0)
+        for w in words:
+            a = stride + ((w * np.uint64(size - stride)) >> np.uint64(32)).astype(np.int64)
+            s = (head - 1 - a) % capacity
+            n = (s + stride) % capacity
+            take = ~valid & ~first[n]
+            anchor[take], succ[take] = s[take], n[take]
+            valid |= take
+    anchor[~valid] = s[~valid]
+    succ[~valid] = anchor[~valid]
+    return anchor, succ, _frame_table(anchor, succ, head, size, capacity, stride, stack, first), valid
+
+
+def given_transitions(index, head: int, size: int, capacity: int, stride: int, stack: int, first):
+    """:func:`philox_transitions` for given anchors ``index`` (reduced mod
+    ``capacity``): valid iff ``stride <= age(anchor) < size`` and the successor
+    is no ``first`` frame; an invalid image has ``successor = anchor``."""
+    head, size, capacity, stride, stack, first = _ring_args(head, size, capacity, stride, stack, first)
+    anchor = np.asarray(index, np.int64).reshape(-1) % capacity
+    succ = (anchor + stride) % capacity
+    age = (head - 1 - anchor) % capacity
+    valid = (age >= stride) & (age < size) & ~first[succ]
+    succ = np.where(valid, succ, anchor)
+    return anchor, succ, _frame_table(anchor, succ, head, size, capacity, stride, stack, first), valid
+
+
+def transition_windows(crop: Crop, H: int, W: int, B: int, seed: int = 0, counter: int = 0, shared_window=False):
+    """int32 [2, B, 3]: the windows of the observation stacks and of the next
+    stacks of one :func:`replay_transitions` launch.  A random crop draws the
+    first from Philox block 1 (:func:`philox_windows`) and the second from
+    block 5 -- or repeats the first with ``shared_window``; ``'center'`` and
+    ``origin=`` give both the window of :func:`crop_windows`."""
+    if crop.kind != 'random':
+        w = crop_windows(crop, H, W, B)
+        return np.stack([w, w])
+    w0 = philox_windows(seed, counter, B, crop, H, W)
+    return np.stack([w0, w0 if shared_window else philox_windows(seed, counter, B, crop, H, W, block=5)])
+
+
+def _transition_cfg(cfg, where):
+    if cfg.colour_kernel:
+        raise ValueError(f'{where} does not apply colour matrices')
+    if cfg.resize is not None:
+        raise ValueError(f'{where}: a resize is not supported on the replay path')
+    if cfg.layout != 'nchw':
+        raise ValueError(f'{where}: frames are stacked along channels of an NCHW tensor; NHWC stacks are not supported')
+
+
+def replay_transitions(store, head: int, size: int, batch: int, cfg: DecodeConfig = DecodeConfig(), stack: int = 1,
+                       stride: int = 1, first=None, seed: int = 0, counter=None, index=None, meta=None,
+                       next_meta=None, shared_window: bool = False, state=None):
+    """Frame-stacked transitions out of a frame-once store, in ONE launch of
+    the gfx950 kernel: ``(stacks, info)``.
+
+    ``store`` (u8 [capacity, H, W, C]) is a ring filled in lockstep, ``stride``
+    frames per environment step; ``head`` is the next slot written and
+    ``size`` the number of stored frames; ``first`` (u8 / bool [capacity]) marks
+    the first observation after a reset.  The launch draws ``batch`` anchors
+    (:func:`philox_transitions`; or takes ``index``:
+    :func:`given_transitions`), and decodes for each the last ``stack`` frames
+    ending at the anchor and the ``stack`` frames ending one step later,
+    stacked along channels, oldest first::
+
+        stacks [2, batch, stack * Cout, h, w]      # stacks[0] = obs, stacks[1] = next_obs
+
+    With ``cfg.crop`` one window serves all frames of a stack, and the two
+    stacks of a transition take independent windows
+    (:func:`transition_windows`) unless ``shared_window``.  The values are
+    :func:`replay_sample`'s bit for bit.  ``info`` holds ``index`` and
+    ``next_index`` (int64 [batch]), ``valid`` (bool [batch]; False where no
+    candidate avoided an episode boundary: the image is a stack of real
+    frames with ``next_index == index``), ``crop`` / ``next_crop`` (int32
+    [batch, 3], with a crop), ``meta`` (rows of ``meta`` at the anchor) and
+    ``next_meta`` (rows of ``next_meta`` at the successor).
+
+    ``counter`` as in :func:`replay_sample`.  ``state``: a device int64 [2]
+    holding (head, size), read by the kernel instead of the arguments -- a
+    captured graph then follows a store that grows between replays.
+
+    Only NCHW output: channel-stacked NHWC needs another store pattern."""
+    import torch
+    ext = hip_ext()
+    if store.dtype != torch.uint8 or not store.is_cuda or store.dim() != 4 or not store.is_contiguous():
+        raise TypeError('replay_transitions expects a contiguous uint8 [N,H,W,C] device tensor')
+    _transition_cfg(cfg, 'replay_transitions')
+    N, H, W, C = store.shape
+    if max(cfg.cmap) >= C:
+        raise ValueError(f'channel map {cfg.cmap} needs more than {C} input channels')
+    dev = store.device
+    if first is None:
+        raise ValueError('replay_transitions needs the first column (episode starts)')
+    if first.device != dev or first.dtype not in (torch.uint8, torch.bool) or tuple(first.shape) != (N,) \
+            or not first.is_contiguous():
+        raise ValueError(f'first must be a contiguous uint8 / bool [{N}] tensor on {dev}')
+    state_ptr = 0
+    if state is not None:
+        if state.dtype != torch.int64 or state.numel() != 2 or state.device != dev or not state.is_contiguous():
+            raise ValueError('state must be a contiguous int64 [2] tensor (head, size) on the store\'s device')
+        state_ptr = state.data_ptr()
+    crop, ckw = cfg.crop, {}
+    h, w = (H, W) if crop is None else crop.size
+    info = {}
+    if crop is not None:
+        crop.check_frame(H, W)
+        info['crop'] = torch.empty((batch, 3), dtype=torch.int32, device=dev)
+        info['next_crop'] = torch.empty((batch, 3), dtype=torch.int32, device=dev)
+        ckw = dict(crop_size=list(crop.size), crop_mode=crop.mode, crop_origin=list(crop.origin or ()),
+                   crop_pad=crop.pad, mirror=crop.mirror, x_align=crop.x_align,
+                   window_key=(int(seed) + crop.seed) & (2 ** 64 - 1), shared_window=int(bool(shared_window)),
+                   crop_out=info['crop'].data_ptr(), next_crop_out=info['next_crop'].data_ptr())
+    out = torch.empty((2, batch, int(stack) * cfg.cout, h, w), dtype=cfg.torch_dtype(), device=dev)
+    idx_out = torch.empty(batch, dtype=torch.int64, device=dev)
+    nidx_out = torch.empty(batch, dtype=torch.int64, device=dev)
+    valid = torch.empty(batch, dtype=torch.bool, device=dev)
+    idx_in, ctr_ptr, ctr_value = 0, 0, 0
+    if index is not None:
+        index = index.to(dev, torch.int64).contiguous()
+        if index.numel() != batch:
+            raise ValueError('index needs one entry per image')
+        idx_in = index.data_ptr()
+    if index is not None and not (crop is not None and crop.kind == 'random'):
+        counter = None          # nothing is drawn
+    elif isinstance(counter, torch.Tensor):
+        if counter.dtype != torch.int64 or counter.numel() < 1 or counter.device != dev:
+            raise ValueError('a device counter must be an int64 tensor on the store\'s device')
+        ctr_ptr = counter.data_ptr()
+    elif counter is not None:
+        ctr_value = int(counter) & (2 ** 64 - 1)
+    else:
+        raise ValueError('drawing anchors or windows needs a counter (int or device tensor)')
+
+    def columns(cols):
+        mout, src, dst, nbytes = {}, [], [], []
+        for k, col in (cols or {}).items():
+            if col.device != dev or not col.is_contiguous() or col.shape[0] != N:
+                raise ValueError(f'metadata column {k!r} must be a contiguous [{N}, ...] tensor on {dev}')
+            o = torch.empty((batch,) + tuple(col.shape[1:]), dtype=col.dtype, device=dev)
+            mout[k] = o
+            src.append(col.data_ptr())
+            dst.append(o.data_ptr())
+            nbytes.append(col[0].numel() * col.element_size())
+        return mout, src, dst, nbytes
+    info['meta'], src, dst, nbytes = columns(meta)
+    info['next_meta'], nsrc, ndst, nnbytes = columns(next_meta)
+    lut = device_lut(cfg, dev)
+    ext.replay_transitions(store.data_ptr(), N, int(head), int(size), state_ptr, first.data_ptr(), int(stack),
+                           int(stride), out.data_ptr(), lut.data_ptr(), batch, H, W, C, cfg.cout, cfg.cmap,
+                           int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], int(seed) & (2 ** 64 - 1),
+                           ctr_ptr, ctr_value, idx_in, idx_out.data_ptr(), nidx_out.data_ptr(), valid.data_ptr(),
+                           src, dst, nbytes, nsrc, ndst, nnbytes, _stream(dev), table_only(cfg, dev), **ckw)
+    info.update(index=idx_out, next_index=nidx_out, valid=valid)
+    return out, info
 
 
 def color4x4(images, M=None, bias=(0.0, 0.0, 0.0, 0.0), gamma=None, flip=False, cout=4, jitter=None, pivot=127.5):
