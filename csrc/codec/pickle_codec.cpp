@@ -464,7 +464,7 @@ VPtr parse(const uint8_t* data, size_t n) {
 namespace {
 
 struct Light {   // (no initialisers: the scanner's arrays stay unwritten until used)
-  enum Kind : uint8_t { OTHER, INT, STR, TUPLE, ROOT } kind;
+  enum Kind : uint8_t { OTHER, INT, STR, TUPLE, ROOT, BYTES } kind;   // BYTES: its span in `s`
   uint16_t kid0, nkids;   // TUPLE: its elements in the arena
   int64_t i;
   Span s;
@@ -599,8 +599,10 @@ class DescriptorScanner {
   }
   bool skip_bytes(uint64_t k) {
     if (k > n_ - p_) return false;
+    Light v(Light::BYTES);
+    v.s.p = reinterpret_cast<const char*>(d_ + p_), v.s.n = size_t(k);
     p_ += size_t(k);
-    return push(Light(Light::OTHER));
+    return push(v);
   }
   bool make_tuple(size_t k) {
     if (k > h_ || floor() > h_ - k || narena_ + k > kArena) return false;
@@ -624,7 +626,7 @@ class DescriptorScanner {
       if (out_->has_origin || v.kind != Light::STR) return false;
       out_->has_origin = true, out_->origin = v.s;
     } else if (k.s.is("_btshm")) {
-      if (seen_shm_ || v.kind != Light::TUPLE || v.nkids < 8 || v.nkids > 10) return false;
+      if (seen_shm_ || v.kind != Light::TUPLE || v.nkids < 8 || v.nkids > 11) return false;
       seen_shm_ = true;
       const Light* e = &arena_[v.kid0];
       if (e[0].kind != Light::STR || e[6].kind != Light::STR || e[7].kind != Light::INT) return false;
@@ -646,7 +648,7 @@ class DescriptorScanner {
         }
         out_->tag_elems = tn;
       }
-      if (v.nkids == 10) {
+      if (v.nkids >= 10) {
         if (e[9].kind != Light::TUPLE || e[9].nkids != 5) return false;
         const Light* t = &arena_[e[9].kid0];
         for (int i = 0; i < 5; ++i) {
@@ -654,6 +656,15 @@ class DescriptorScanner {
           out_->delta[i] = t[i].i;
         }
         out_->has_delta = true;
+      }
+      // element 10 (band_rows, mask bytes); anything else there means "no mask"
+      if (v.nkids == 11 && e[10].kind == Light::TUPLE && e[10].nkids == 2) {
+        const Light* t = &arena_[e[10].kid0];
+        if (t[0].kind == Light::INT && t[1].kind == Light::BYTES && t[0].i >= 1 && t[0].i <= (int64_t(1) << 15) &&
+            t[1].s.n >= 2 && t[1].s.n % 2 == 0 && t[1].s.n <= 2 * size_t(kMaxMaskWords)) {
+          out_->band_rows = int(t[0].i);
+          out_->mask = reinterpret_cast<const uint8_t*>(t[1].s.p), out_->mask_bytes = t[1].s.n;
+        }
       }
     }
     return true;

@@ -96,7 +96,7 @@ VPtr parse(const uint8_t* data, size_t n);
 // --------------------------------------------------------------------------
 // What the GPU loader's worker needs of a shared-memory descriptor message
 // ({'btid': .., 'xy': .., '_btshm': (segment, slot, offset, H, W, C, key,
-// generation[, tag[, delta]])}, see csrc/sim/cubesim.cpp), found in one pass
+// generation[, tag[, delta[, blocks]]])}, see csrc/sim/cubesim.cpp), found in one pass
 // over the opcodes with no heap allocation: parse() builds ~40 shared nodes
 // for such a message, and the worker reads three of its entries.  Strings
 // are spans of the message.
@@ -106,10 +106,11 @@ struct Span {
   bool is(const char* s) const { return n == std::char_traits<char>::length(s) && std::memcmp(p, s, n) == 0; }
   std::string str() const { return std::string(p ? p : "", n); }
 };
+constexpr int kMaxMaskWords = 64;
 struct DescriptorScan {
   Span segment, image_key;        // elements 0 and 6
   int64_t slot = 0, offset = 0, h = 0, w = 0, c = 0, gen = 0;   // elements 1..5 and 7
-  int elems = 0;                  // elements in the tuple (8..10)
+  int elems = 0;                  // elements in the tuple (8..11)
   // element 8 when it is a tuple (a non-tuple, e.g. None, means "no tag"):
   // ('rgb_a',) or ('tile16', key segment, key generation)
   int tag_elems = 0;              // 0: no tag tuple
@@ -117,6 +118,13 @@ struct DescriptorScan {
   int64_t tag2 = 0;               // its third element (3-element tags)
   bool has_delta = false;         // element 9 is a tuple of 5 integers ...
   int64_t delta[5] = {0, 0, 0, 0, 0};   // ... (base_gen, y0, y1, x0, x1)
+  // element 10 when it is (band_rows, mask): a positive int and a bytes object
+  // of 1..kMaxMaskWords little-endian uint16 words (shmring.h: kWantSlotBlocks)
+  // -- the mask stays where it lies in the message.  Anything else in that
+  // place means "no mask" (band_rows 0), never a failed scan.
+  int band_rows = 0;
+  const uint8_t* mask = nullptr;
+  size_t mask_bytes = 0;
   bool has_origin = false;
   Span origin;                    // 'origin' entry (a str)
   bool has_btid = false;

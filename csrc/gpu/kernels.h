@@ -166,6 +166,30 @@ struct DeltaParams {
 bool decode_delta_supported(const DecodeParams& p);
 hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t stream);
 
+// decode_delta() with a block mask per image in place of a rectangle (csrc/
+// common/block_mask.h): every image is cut into blocks of 64 pixel columns x
+// band_rows stored rows on an absolute grid; bit c of mask[b][k] set means
+// the block in band k (stored rows [k * band_rows, (k + 1) * band_rows),
+// the last band may be partial), columns [64c, 64c + 63], comes from
+// p.srcs[b] and is written, raw, to mirror[b]; every other block comes from
+// mirror[b].  After the launch mirror[b] equals the frame.  mirror[b] ==
+// nullptr: the whole image from p.srcs[b], nothing stored, mask[b] ignored.  Values are bit-identical to decode()'s.  On top of
+// decode_delta()'s launch-wide conditions: p.B <= kMaxBlockImgs, W % 64 == 0,
+// W <= 1024, band_rows a power of two with at most kMaxBlockBands bands,
+// and no mask bit outside the frame.  Anything else is hipErrorInvalidValue,
+// checked on the host: nothing is launched.  The masks travel in the kernel
+// arguments (no copy or launch of their own), hence the limits; a caller with
+// more images splits the launch.  p.unroll is ignored.
+constexpr int kMaxBlockImgs = 32;
+constexpr int kMaxBlockBands = 30;
+struct BlockParams {
+  uint8_t* mirror[kMaxBlockImgs] = {};
+  int band_rows = 0;
+  uint16_t mask[kMaxBlockImgs][kMaxBlockBands] = {};
+};
+bool decode_delta_blocks_supported(const DecodeParams& p);   // the launch-wide conditions
+hipError_t decode_delta_blocks(const DecodeParams& p, const BlockParams& d, hipStream_t stream);
+
 // Key-frame delta frames (csrc/codec/tiledelta.h), decoded in two launches
 // on `stream` with the same table, channel map, dtype and layout as decode():
 //   1. output image b <- fills[b]: its producer's key frame, already decoded

@@ -704,6 +704,62 @@ __global__ __launch_bounds__(kBlock) void decode_delta_kernel(DecodeParams p, De
   }
 }
 
+// decode_delta_kernel with a block mask as the inside test (kernels.h:
+// decode_delta_blocks): band sy >> log2(band_rows), column block x >> 6, one
+// bit.  Blocks are 64 pixels wide on an absolute grid and W % 64 == 0, so a
+// group (PPT <= 16 pixels of one row, W % PPT == 0) never straddles one.  The
+// masks arrive in the kernel arguments and are staged to LDS beside the value
+// table: row b holds image b's band words.
+constexpr int kBlockRowWords = 32;   // uint16 per image: kMaxBlockBands words, padded
+struct BlockArgs {
+  uint8_t* mirror[kMaxBlockImgs];
+  uint16_t rows[kMaxBlockImgs][kBlockRowWords];
+  int band_log2;
+};
+static_assert(kMaxBlockBands <= kBlockRowWords, "a row holds the band words");
+static_assert(sizeof(DecodeParams) + sizeof(BlockArgs) <= 4096, "both structs travel as kernel arguments");
+
+template <int PPT, int CIN, int OUTT, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void decode_delta_blocks_kernel(DecodeParams p, BlockArgs d) {
+  __shared__ uint32_t tab[kTabWords];
+  __shared__ uint32_t msk[kMaxBlockImgs * kBlockRowWords / 2];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&d.rows[0][0]);
+    for (int i = threadIdx.x; i < p.B * (kBlockRowWords / 2); i += kBlock) msk[i] = src[i];
+  }
+  __syncthreads();
+  const uint16_t* rows = reinterpret_cast<const uint16_t*>(msk);
+
+  const int64_t HW = int64_t(p.H) * p.W;
+  const int64_t groups_per_img = HW / PPT;
+  const int64_t total = groups_per_img * p.B;
+  const int cout = p.Cout;
+  int cm[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) cm[c] = p.cmap[c];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  const bool small = total + stride < (int64_t(1) << 31) && HW < (int64_t(1) << 31);
+
+  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += stride) {
+    Group gr;
+    int y, x;
+    split_group<PPT>(g, groups_per_img, p.W, small, gr.b, gr.q, y, x);
+    const int b = gr.b;
+    const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
+    const int64_t off = (int64_t(sy) * p.W + x) * CIN;
+    uint8_t* mir = d.mirror[b];
+    const uint32_t word = rows[b * kBlockRowWords + (sy >> d.band_log2)];   // (band < kMaxBlockBands: checked on the host)
+    const bool inside = mir == nullptr || ((word >> (x >> 6)) & 1u) != 0;
+    const uint8_t* base = inside ? p.srcs[b] : mir;
+    gr.src = base + off;
+    Pixels<PPT, CIN> px;
+    load_pixels<PPT, CIN>(gr.src, px);
+    if (inside && mir != nullptr) store_pixels<PPT, CIN>(mir + off, px);
+    emit<PPT, CIN, OUTT, LAYOUT>(p, xf, cm, cout, HW, gr, px);
+  }
+}
+
 int grid_for(int64_t work, int cap = 0) {
   // Measured on MI355X (profiles/decode_unroll_sweep.txt): up to ~4k blocks
   // of work, one resident wave of 2048 blocks (256 CUs x 8) is best; for
@@ -1272,6 +1328,20 @@ hipError_t launch_delta_out(const DecodeParams& p, const DeltaParams& d, hipStre
   return hipGetLastError();
 }
 
+template <int OUTT>
+hipError_t launch_blocks_out(const DecodeParams& p, const BlockArgs& d, hipStream_t s) {
+  constexpr int PPT = delta_ppt(OUTT);
+  const int grid = grid_for(int64_t(p.B) * p.H * p.W / PPT, p.max_grid);
+  if (p.Cin == 4) {
+    if (p.layout == NCHW) decode_delta_blocks_kernel<PPT, 4, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_delta_blocks_kernel<PPT, 4, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+  } else {
+    if (p.layout == NCHW) decode_delta_blocks_kernel<PPT, 3, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_delta_blocks_kernel<PPT, 3, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 bool decode_delta_supported(const DecodeParams& p) {
@@ -1307,6 +1377,42 @@ hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t
     case OUT_BF16: return launch_delta_out<OUT_BF16>(p, d, stream);
     case OUT_F16: return launch_delta_out<OUT_F16>(p, d, stream);
     case OUT_U8: return launch_delta_out<OUT_U8>(p, d, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+bool decode_delta_blocks_supported(const DecodeParams& p) {
+  return p.B <= kMaxBlockImgs && p.W % 64 == 0 && p.W <= 1024 && decode_delta_supported(p);
+}
+
+hipError_t decode_delta_blocks(const DecodeParams& p, const BlockParams& d, hipStream_t stream) {
+  // every condition is checked here, before anything is launched
+  if (p.B == 0) return hipSuccess;
+  if (!decode_delta_blocks_supported(p)) return hipErrorInvalidValue;
+  const size_t elem = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 1 : 2);
+  if (!p.ndsts && (size_t(p.H) * p.W * p.Cout * elem) % 16 != 0) return hipErrorInvalidValue;
+  BlockArgs a = {};
+  const unsigned cols = (2u << unsigned((p.W - 1) / 64)) - 1u;
+  const int br = d.band_rows;
+  if (br <= 0 || (br & (br - 1)) != 0) return hipErrorInvalidValue;
+  const int nb = (p.H + br - 1) / br;
+  if (nb > kMaxBlockBands) return hipErrorInvalidValue;   // (so every row's band index stays inside a mask row)
+  while ((1 << a.band_log2) < br) ++a.band_log2;
+  for (int b = 0; b < p.B; ++b) {
+    a.mirror[b] = d.mirror[b];
+    if (!d.mirror[b]) continue;
+    if ((reinterpret_cast<uintptr_t>(d.mirror[b]) % 16) != 0) return hipErrorInvalidValue;
+    for (int k = 0; k < kMaxBlockBands; ++k) {
+      const unsigned w = d.mask[b][k];
+      if (k >= nb ? w != 0 : (w & ~cols) != 0) return hipErrorInvalidValue;   // a bit outside the frame
+      a.rows[b][k] = uint16_t(w);
+    }
+  }
+  switch (p.out_dtype) {
+    case OUT_F32: return launch_blocks_out<OUT_F32>(p, a, stream);
+    case OUT_BF16: return launch_blocks_out<OUT_BF16>(p, a, stream);
+    case OUT_F16: return launch_blocks_out<OUT_F16>(p, a, stream);
+    case OUT_U8: return launch_blocks_out<OUT_U8>(p, a, stream);
   }
   return hipErrorInvalidValue;
 }

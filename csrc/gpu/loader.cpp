@@ -133,6 +133,9 @@ void PinnedPool::release(void* owner, Buffer* b) {
 // StreamLoader
 // ---------------------------------------------------------------------------
 StreamLoader::StreamLoader(const LoaderConfig& cfg) : cfg_(cfg) {
+  // BT_SLOT_BLOCKS=0 keeps the rectangle path (decode_delta) for A/B runs: no
+  // block hint to the producers, no block-mask launches
+  if (const char* e = std::getenv("BT_SLOT_BLOCKS")) slot_blocks_ = std::strcmp(e, "0") != 0;
   if (cfg_.addresses.empty()) throw std::invalid_argument("StreamLoader: no addresses");
   if (cfg_.batch_size < 1) throw std::invalid_argument("StreamLoader: batch_size < 1");
   // the value table (kernels.h): a bare [4][256] fp32 table is padded with a
@@ -692,6 +695,12 @@ bool StreamLoader::process(zmtp::Message&& msg) {
       }
       if (!ok) return bad("malformed _btshm delta");
       it.has_delta = true;
+      // element 11: a mask that does not fit the frame means "no mask"
+      if (sc.band_rows > 0) {
+        mirror::BlockReport br;
+        br.band_rows = sc.band_rows, br.mask = sc.mask, br.bytes = sc.mask_bytes;
+        it.has_blocks = mirror::blocks_from_report(br, h, w, &it.blocks);
+      }
     }
     if (has_codec && sc.tag0.is(planar::kName)) {
       const size_t slot_lo = it.seg->slot_offset(it.slot);
@@ -749,6 +758,16 @@ bool StreamLoader::process(zmtp::Message&& msg) {
       }
       if (!ok) return bad("malformed _btshm delta");
       it.has_delta = !has_codec || (d.items[8]->items.size() == 1);   // raw and rgb_a frames only
+      if (it.has_delta && d.items.size() >= 11 && d.items[10]->kind == codec::Value::TUPLE &&
+          d.items[10]->items.size() == 2 && d.items[10]->items[0]->kind == codec::Value::INT &&
+          d.items[10]->items[1]->kind == codec::Value::BYTES) {
+        // 11th element (band_rows, mask): which blocks of the rectangle (shmring.h); malformed = no mask
+        const codec::Value& bv = *d.items[10];
+        mirror::BlockReport br;
+        br.band_rows = bv.items[0]->i >= 1 && bv.items[0]->i <= (int64_t(1) << 15) ? int(bv.items[0]->i) : 0;
+        br.mask = bv.items[1]->ptr(data), br.bytes = bv.items[1]->len;
+        it.has_blocks = mirror::blocks_from_report(br, h, w, &it.blocks);
+      }
     }
     const codec::Value* tag = has_codec ? d.items[8].get() : nullptr;
     if (tag && tag->items.size() == 1 && tag->items[0]->kind == codec::Value::STR && tag->items[0]->s == planar::kName) {
@@ -1048,7 +1067,8 @@ StreamLoader::MappedSegment& StreamLoader::segment(std::string_view name_view) {
   // pulls over the link; anything else needs interleaved pixels
   ms.seg->add_hint(reads_rgb_only() && ms.dev_base ? shm::kWantPlanarAlpha : shm::kNeedInterleaved);
   // ... and that it keeps slot copies: the producer may report what it rewrote
-  if (mirror_wanted() && ms.dev_base) ms.seg->add_hint(shm::kWantSlotDelta);
+  // (and, unless BT_SLOT_BLOCKS=0, which blocks of the rectangle: shmring.h kWantSlotBlocks)
+  if (mirror_wanted() && ms.dev_base) ms.seg->add_hint(shm::kWantSlotDelta | (slot_blocks_ ? shm::kWantSlotBlocks : 0u));
   ms.ring = mirror::Ring(ms.seg->nslots());
   {
     std::lock_guard<std::mutex> lk(mu_);
@@ -1602,12 +1622,84 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     // that launch takes from the copy was written by earlier, whole reads.
     // reap() / promote_ready() invalidate the slot's entry all the same, so
     // nothing later relies on a copy a torn read produced.
+    // With block masks the same holds block by block: a producer that takes a
+    // slot back first restores what the slot's last frame drew -- pixels of
+    // this frame's spans, which the next frame's mask contains because it is
+    // the union of both frames' blocks -- and then draws the next frame, whose
+    // spans are in that mask too.  It writes nowhere else, so torn bytes lie
+    // inside the next frame's set blocks and are read again from the host.
+    //
+    // Frames that admit a block grid (W % 64 == 0, W <= 1024) take
+    // decode_delta_blocks whether their producer sent a mask or only a
+    // rectangle (the mask is then built from the widened rectangle), at most
+    // kMaxBlockImgs images per launch; other sizes, and BT_SLOT_BLOCKS=0, keep
+    // decode_delta.
     const bool mirror_on = plain && !cfg_.crop && !cfg_.resize && mirror_wanted();
+    auto run_blocks = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
+      const size_t frame = size_t(H_) * W_ * size_t(sp.Cin);
+      uint64_t saved = 0, deltas = 0, fine = 0;
+      hipError_t err = hipSuccess;
+      // the masks travel in the kernel arguments: at most kMaxBlockImgs images per launch
+      for (size_t lo = 0; lo < imgs.size() && err == hipSuccess; lo += size_t(kMaxBlockImgs)) {
+        const size_t n_here = std::min(imgs.size() - lo, size_t(kMaxBlockImgs));
+        DecodeParams part = sp;
+        BlockParams bp;
+        bp.band_rows = blocks::band_rows_for(H_);   // one grid per frame size (slot_mirror.h: decide_blocks)
+        if (lo != 0 || n_here != imgs.size()) {
+          std::memset(part.flip_bits, 0, sizeof(part.flip_bits));
+          for (size_t n = 0; n < n_here; ++n) {
+            part.srcs[n] = sp.srcs[lo + n];
+            if (sp.ndsts) part.dsts[n] = sp.dsts[lo + n];
+            if ((sp.flip_bits[(lo + n) >> 6] >> ((lo + n) & 63)) & 1) part.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
+          }
+          part.B = part.nsrcs = int(n_here);
+          if (sp.ndsts) part.ndsts = int(n_here);
+          else part.dst = static_cast<uint8_t*>(sp.dst) + lo * out_img_bytes;   // one dense batch: this part's images
+        }
+        for (size_t n = 0; n < n_here; ++n) {
+          const Item& it = *imgs[lo + n];
+          // the kernel reads this image in its ring slot?  (not a frame staged or rebuilt elsewhere)
+          if (!it.ms || it.staged || !it.expanded.empty()) continue;
+          uint8_t* m = slot_mirror(*it.ms, sp.Cin, it.has_delta);
+          if (!m) {   // not mirrored (now): whatever the copy held for this slot is no base for a later report
+            it.ms->ring.invalidate(it.slot);
+            continue;
+          }
+          bool used = false, masked = false;
+          const mirror::BlockMask bm = it.ms->ring.decide_blocks(it.slot, it.gen, it.has_delta ? &it.delta : nullptr,
+                                                                 it.has_blocks ? &it.blocks : nullptr, H_, W_, &used, &masked);
+          bp.mirror[n] = m + size_t(it.slot) * frame;
+          std::memcpy(bp.mask[n], bm.w, sizeof(bp.mask[n]));
+          if (used) {
+            deltas++;
+            fine += masked;
+            saved += uint64_t(int64_t(H_) * W_ - bm.pixels(H_)) * uint64_t(sp.Cin);
+          }
+        }
+        bool any = false;
+        for (size_t n = 0; n < n_here; ++n) any = any || bp.mirror[n] != nullptr;
+        err = any ? decode_delta_blocks(part, bp, st) : decode(part, st);
+      }
+      {
+        // only the set blocks cross the link: take back what process() counted for whole frames
+        std::lock_guard<std::mutex> lk(mu_);
+        stats_.delta_frames += deltas;
+        stats_.block_frames += fine;
+        stats_.image_bytes -= saved;
+      }
+      return err;
+    };
     auto run_plain = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
       if (!mirror_on) return decode(sp, st);
       // (RGBA -> RGBA u8 NHWC keeps decode()'s 4-pixel host-read shape, kernels.hip launch_out: not mirrored)
       const bool raw_rgba = sp.out_dtype == OUT_U8 && sp.layout == NHWC && sp.Cin == 4 && sp.Cout == 4;
       const bool ok = !raw_rgba && decode_delta_supported(sp);
+      if (ok && slot_blocks_ && blocks::width_ok(W_)) {
+        bool any_ring = false;
+        for (const Item* it : imgs) any_ring = any_ring || (it->ms && !it->staged && it->expanded.empty());
+        if (any_ring) return run_blocks(sp, imgs);
+        return decode(sp, st);
+      }
       DeltaParams dl;
       bool any = false;
       uint64_t saved = 0, deltas = 0;

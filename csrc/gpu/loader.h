@@ -331,6 +331,7 @@ struct LoaderStats {
   uint64_t tiled_frames = 0;               // key-frame delta frames (tiledelta.h)
   uint64_t planar_frames = 0;              // shm frames that arrived as rgb_a (planar_alpha.h)
   uint64_t delta_frames = 0;               // frames of which only the reported region was read from the host
+  uint64_t block_frames = 0;               // ... of which only the reported blocks were (subset of delta_frames)
   uint64_t mirror_bytes = 0;               // HBM held by slot mirrors
   double h2d_issue_ms = 0;
   // GPU time of one launch per kTimedEveryImages images (timing events around
@@ -384,6 +385,8 @@ class StreamLoader {
     MappedSegment* ms = nullptr;       // the ring `seg` belongs to (slot mirror)
     bool has_delta = false;            // descriptor element 10 (shmring.h: kWantSlotDelta)
     mirror::Delta delta;
+    bool has_blocks = false;           // ... and a valid element 11 (shmring.h: kWantSlotBlocks)
+    mirror::BlockMask blocks;
     bool flip = false;
     // key-frame delta (csrc/codec/tiledelta.h): `src`/`dsrc` point at the
     // encoded frame (ntiles payload tiles); the key frame is at key_host (shm)
@@ -520,6 +523,7 @@ class StreamLoader {
     mirror::Ring ring;
   };
   bool mirror_wanted() const;                           // this loader's configuration can use slot mirrors
+  bool slot_blocks_ = true;                             // block masks (decode_delta_blocks) unless BT_SLOT_BLOCKS=0
   uint8_t* slot_mirror(MappedSegment& ms, int cin, bool reported);   // the ring's mirror for such frames, or null
   void invalidate_mirror(shm::Segment* seg, uint32_t slot);
   std::map<const shm::Segment*, MappedSegment*> by_seg_;

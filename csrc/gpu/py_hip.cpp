@@ -345,6 +345,47 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("dsts") = std::vector<uintptr_t>(),
         py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0);
 
+  // Block-mask read + slot mirror (kernels.h: decode_delta_blocks) at the pointer level: as decode_delta, with
+  // band_rows (one grid per launch) and masks[b] (one uint16 word per band, at most 30) in place of a region.
+  m.def("decode_delta_blocks",
+        [](std::vector<uintptr_t> srcs, std::vector<uintptr_t> mirrors, int band_rows,
+           std::vector<std::vector<int>> masks, uintptr_t dst, uintptr_t lut, int B, int H, int W, int Cin, int Cout,
+           std::vector<int> cmap, int flip_all, int out_dtype, int layout, uintptr_t stream, std::vector<uintptr_t> dsts,
+           std::vector<uint64_t> flip_bits, int max_grid) {
+          // (more than kMaxBlockImgs images: decode_delta_blocks itself refuses the launch; only the first ones are filled in)
+          if (B < 0 || B > kMaxSrcs || srcs.size() > size_t(kMaxSrcs) || dsts.size() > size_t(kMaxSrcs))
+            throw std::invalid_argument("decode_delta_blocks: at most kMaxSrcs (64) image pointers");
+          if (mirrors.size() != size_t(B) || masks.size() != size_t(B))
+            throw std::invalid_argument("decode_delta_blocks: mirrors and masks hold one entry per image");
+          DecodeParams p;
+          fill_image_lists(p, srcs, dsts, flip_bits, "decode_delta_blocks");
+          BlockParams d;
+          d.band_rows = band_rows;
+          for (int b = 0; b < B && b < kMaxBlockImgs; ++b) {
+            d.mirror[b] = ptr<uint8_t>(mirrors[size_t(b)]);
+            const std::vector<int>& mk = masks[size_t(b)];
+            if (mk.size() > size_t(kMaxBlockBands))
+              throw std::invalid_argument("decode_delta_blocks: at most kMaxBlockBands (30) bands per image");
+            for (size_t k = 0; k < mk.size(); ++k) {
+              if (mk[k] < 0 || mk[k] > 0xffff) throw std::invalid_argument("decode_delta_blocks: a mask word is a uint16");
+              d.mask[b][k] = uint16_t(mk[k]);
+            }
+          }
+          p.max_grid = max_grid;
+          p.dst = ptr<void>(dst);
+          p.lut = ptr<const float>(lut);
+          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+          fill_cmap(p.cmap, cmap);
+          p.flip_all = flip_all;
+          p.out_dtype = out_dtype;
+          p.layout = layout;
+          check(decode_delta_blocks(p, d, stream_of(stream)), "decode_delta_blocks");
+        },
+        py::arg("srcs"), py::arg("mirrors"), py::arg("band_rows"), py::arg("masks"), py::arg("dst"), py::arg("lut"),
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("cmap"), py::arg("flip_all"),
+        py::arg("out_dtype"), py::arg("layout"), py::arg("stream"), py::arg("dsts") = std::vector<uintptr_t>(),
+        py::arg("flip_bits") = std::vector<uint64_t>(), py::arg("max_grid") = 0);
+
   // Key-frame delta decode (kernels.h: decode_tiles) at the pointer level: srcs[b] the encoded frame,
   // fills[b] image b's decoded key frame, tile_start the prefix sums of the payload tile counts.
   m.def("decode_tiles",
@@ -1629,6 +1670,7 @@ PYBIND11_MODULE(_hip, m) {
         d["tiled_frames"] = s.tiled_frames;
         d["planar_frames"] = s.planar_frames;
         d["delta_frames"] = s.delta_frames;
+        d["block_frames"] = s.block_frames;
         d["mirror_bytes"] = s.mirror_bytes;
         d["timed_launches"] = s.timed_launches;
         d["timed_images"] = s.timed_images;

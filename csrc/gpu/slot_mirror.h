@@ -8,14 +8,22 @@
 // outside stored rows [y0, y1] x pixel columns [x0, x1] equals what the slot
 // held when it was published with generation base_gen.
 //
+// A producer asked with kWantSlotBlocks adds element 11, (band_rows, mask):
+// the same statement for the blocks of a 64-column x band_rows grid that are
+// not set in the mask (csrc/common/block_mask.h) -- about two thirds of the
+// widened rectangle's bytes for the cube frames.
+//
 // This header keeps, per mapped ring, which generation the mirror holds for
-// every slot, and decides per frame which region the kernel has to read from
-// the host (kernels.h: decode_delta).  It never looks at pixels.
+// every slot, and decides per frame which region or blocks the kernel has to
+// read from the host (kernels.h: decode_delta, decode_delta_blocks).  It never
+// looks at pixels.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "../common/block_mask.h"
 
 namespace btn {
 namespace gpu {
@@ -61,6 +69,50 @@ inline Region widen(const Region& r, int W) {
   return o;
 }
 
+// Descriptor element 11 as it lies in the message: `bytes` / 2 little-endian
+// uint16 words, one per band of band_rows stored rows (csrc/common/block_mask.h).
+struct BlockReport {
+  int band_rows = 0;
+  const uint8_t* mask = nullptr;
+  size_t bytes = 0;
+};
+
+// A block mask on a grid of its own: bands(H, band_rows) words.
+struct BlockMask {
+  int band_rows = 0;
+  uint16_t w[blocks::kMaxBands] = {};
+  int64_t pixels(int H) const { return blocks::pixels(w, H, band_rows); }
+};
+
+// A reported mask that fits the frame -- a grid the kernel takes, one word per
+// band, no bit past the last column block -- into *out.  False: malformed,
+// which means "no mask" (the rectangle still holds), not an error.
+inline bool blocks_from_report(const BlockReport& b, int H, int W, BlockMask* out) {
+  if (!b.mask || !blocks::geometry_ok(H, W, b.band_rows)) return false;
+  const int nb = blocks::bands(H, b.band_rows);
+  if (b.bytes != size_t(2 * nb)) return false;
+  const unsigned cols = blocks::all_columns(W);
+  BlockMask m;
+  m.band_rows = b.band_rows;
+  for (int k = 0; k < nb; ++k) {
+    const unsigned w = unsigned(b.mask[2 * k]) | (unsigned(b.mask[2 * k + 1]) << 8);
+    if (w & ~cols) return false;
+    m.w[k] = uint16_t(w);
+  }
+  *out = m;
+  return true;
+}
+
+// The blocks a (widened) region touches, on the grid blocks::band_rows_for(H).
+inline BlockMask rect_blocks(const Region& r, int H) {
+  BlockMask m;
+  m.band_rows = blocks::band_rows_for(H);
+  if (r.empty()) return m;
+  const uint16_t bits = blocks::column_bits(r.x0, r.x1);
+  for (int k = r.y0 / m.band_rows; k <= r.y1 / m.band_rows; ++k) m.w[k] = bits;
+  return m;
+}
+
 // HBM the mirrors of one loader may take.
 class Budget {
  public:
@@ -102,6 +154,30 @@ class Ring {
     if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
     if (from_delta) *from_delta = use;
     return r;
+  }
+  // decide() in blocks (decode_delta_blocks): the mask to read from the host,
+  // always on the grid blocks::band_rows_for(H), one grid per launch -- the
+  // reported one (blocks_from_report), when the mirror holds the generation
+  // the report is relative to and the report is on that grid; else one built
+  // from the reported rectangle, widened; else all ones.  The frame must admit a grid (blocks::width_ok(W)).
+  // *from_delta: a report was used; *from_blocks: its mask was.
+  BlockMask decide_blocks(uint32_t slot, uint32_t gen, const Delta* d, const BlockMask* reported, int H, int W,
+                          bool* from_delta = nullptr, bool* from_blocks = nullptr) {
+    BlockMask m;
+    const bool use = d && slot < gen_.size() && holds(slot, d->base_gen) && delta_valid(*d, H, W);
+    const bool fine = use && reported && reported->band_rows == blocks::band_rows_for(H) && blocks::width_ok(W);
+    if (fine) {
+      m = *reported;
+    } else if (use) {
+      m = rect_blocks(widen(d->rect, W), H);
+    } else {
+      m.band_rows = blocks::band_rows_for(H);
+      for (int k = 0, nb = blocks::bands(H, m.band_rows); k < nb; ++k) m.w[k] = blocks::all_columns(W);
+    }
+    if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
+    if (from_delta) *from_delta = use;
+    if (from_blocks) *from_blocks = fine;
+    return m;
   }
 
  private:

@@ -264,6 +264,8 @@ class NativeError(Exception):
   m.attr("RING_VERSION") = shm::kVersion;
   m.attr("WANT_PLANAR_ALPHA") = shm::kWantPlanarAlpha;
   m.attr("NEED_INTERLEAVED") = shm::kNeedInterleaved;
+  m.attr("WANT_SLOT_DELTA") = shm::kWantSlotDelta;
+  m.attr("WANT_SLOT_BLOCKS") = shm::kWantSlotBlocks;
   // An rgb_a frame (csrc/common/planar_alpha.h) at byte offset `off` of a
   // buffer, which ends the frame's slot at `slot_end`: the interleaved
   // H x W x 4 array the CPU dataset path hands out.
@@ -328,6 +330,9 @@ class NativeError(Exception):
     else d["tag"] = py::none();
     if (sc.has_delta) d["delta"] = py::make_tuple(sc.delta[0], sc.delta[1], sc.delta[2], sc.delta[3], sc.delta[4]);
     else d["delta"] = py::none();
+    // element 11 (band_rows, mask) -- the key is there only when the message carries a well-formed one
+    if (sc.band_rows > 0)
+      d["blocks"] = py::make_tuple(sc.band_rows, py::bytes(reinterpret_cast<const char*>(sc.mask), sc.mask_bytes));
     d["origin"] = sc.has_origin ? text(sc.origin) : py::object(py::none());
     d["btid"] = sc.has_btid ? py::object(py::int_(sc.btid)) : py::object(py::none());
     return d;

@@ -20,6 +20,11 @@
 //   csrc/common/planar_alpha.h); auto (default) follows the ring's consumer
 //   hint frame by frame (shmring.h); where the layout does not apply (RGB
 //   frames, tile16, H*W*3 % 16 != 0) frames stay interleaved
+// --render-threads N (env BLENDTORCH_RENDER_THREADS): frames are drawn by N
+//   workers and retired in order, so the stream is the same for any N (only
+//   slot indices may differ); default min(2, CPUs this process may run on)
+//   for a shared-memory ring with codec none -- used only while a consumer
+//   has set the ring's kWantSlotDelta hint -- else 1; tile16 always 1
 // --bench N (no sockets: render N frames into 8 rotating buffers, full vs
 // incremental (DirtyRect) rendering, and report the byte mismatches -- 0;
 // with --shm-layout planar the incremental frames are rgb_a slots, compared
@@ -34,14 +39,18 @@
 // before the kernel socket buffer.
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <memory>
+#include <sched.h>
 #include <unistd.h>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <random>
 #include <string>
 #include <thread>
@@ -49,6 +58,7 @@
 
 #include "../codec/pickle_codec.h"
 #include "../codec/tiledelta.h"
+#include "../common/block_mask.h"
 #include "../common/planar_alpha.h"
 #include "../transport/shmring.h"
 #include "../transport/zmtp.h"
@@ -87,6 +97,7 @@ struct Args {
   bool stamp = false;          // integrity tests: (btid, seq) written into the first image row
   long lease_ms = 30000;       // shm ring: reclaim unclaimed slots after starving this long (shmring.h)
   long long bench = 0;         // >0: offline render benchmark / incremental-render check
+  int render_threads = 0;      // 0: by rule (see above); N: that many render workers
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -100,6 +111,7 @@ Args parse(int argc, char** argv) {
   if (const char* e = std::getenv("BLENDTORCH_SHM_SLOTS")) a.shm_slots = std::atoi(e);
   if (const char* e = std::getenv("BLENDTORCH_SHM_CODEC")) a.codec = e;   // BlenderLauncher(shm_codec=...)
   if (const char* e = std::getenv("BLENDTORCH_SHM_LAYOUT")) a.shm_layout = e;
+  if (const char* e = std::getenv("BLENDTORCH_RENDER_THREADS")) a.render_threads = std::atoi(e);
   std::vector<std::string> v;
   int start = 1;
   for (int i = 1; i < argc; ++i)
@@ -144,6 +156,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--codec") a.codec = need(i), ++i;
     else if (k == "--shm-layout") a.shm_layout = need(i), ++i;
     else if (k == "--bench") a.bench = std::stoll(need(i)), ++i;
+    else if (k == "--render-threads") a.render_threads = std::stoi(need(i)), ++i;
     else if (k == "--resolution") {
       // WxH: render size (render.resolution_x/_y); the camera's field of view is kept
       const std::string r = need(i);
@@ -383,6 +396,14 @@ int main(int argc, char** argv) {
   // with by THIS producer (0: never, or not to be relied on) -- kept here, not
   // read back from the slot word, which a lease reclaim bumps
   std::vector<uint32_t> slot_gen(seg ? size_t(a.shm_slots) : 0, 0u);
+  // kWantSlotBlocks (shmring.h): the blocks each slot's last frame touched
+  // (sim::span_blocks of the record in slot_dirty); a frame's report is that
+  // OR-ed with its own
+  const int band_rows = blocks::band_rows_for(H), nbands = blocks::bands(H, band_rows);
+  int band_log2 = 0;
+  while ((1 << band_log2) < band_rows) ++band_log2;
+  const bool blocks_ok = seg && !tiled && incremental && blocks::geometry_ok(H, W, band_rows);
+  std::vector<uint16_t> slot_mask(blocks_ok ? size_t(a.shm_slots) * size_t(nbands) : 0, uint16_t(0));
   const size_t npix = size_t(W) * H;
   const auto t_start = std::chrono::steady_clock::now();
   auto next_due = t_start;
@@ -390,28 +411,79 @@ int main(int argc, char** argv) {
   int frame = a.frame_start;
   double render_ms = 0;
 
-  while (!g_stop && (a.frames < 0 || published < a.frames)) {
-    pose(frame);
+  // Render workers.  A frame has three parts: a front half on the main thread
+  // (slot acquire, pose -- the RNG, in frame order -- and the metadata part of
+  // the message), the render, and a retire step on the main thread (the
+  // descriptor, publish, faults, send), strictly in dispatch order.  With T
+  // workers up to T + 1 frames are between front half and retire, each in a
+  // slot of its own, so what a consumer receives does not depend on T (only
+  // the slot indices may).  slot_dirty, slot_layout, slot_gen and slot_mask
+  // are touched for a slot only between its acquire and its retire, by the
+  // one frame that holds it.  T = 1 renders on the main thread: the loop of a
+  // single-threaded producer.  tile16 frames build on one another: T = 1.
+  // A worker count taken by rule (no --render-threads) is used only while a
+  // consumer of the ring has set kWantSlotDelta: a loader that reads slots in
+  // place with a mirror can outrun one render thread, whereas behind a copy
+  // path or a training step the second thread would only take CPU from the
+  // consumer -- such a producer draws on its main thread, frame by frame.
+  const bool by_rule = a.render_threads <= 0;
+  int T = a.render_threads;
+  if (T <= 0) {
+    int cpus = 1;
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) cpus = std::max(1, CPU_COUNT(&set));
+    T = seg && !tiled && a.codec == "none" ? std::min(2, cpus) : 1;
+  }
+  if (tiled) T = 1;
+  T = std::min(T, 16);
 
+  struct Job {
+    long long seq = 0;        // dispatch index: the value of `published` when the frame retires
+    int frame = 0;
     int slot = -1;
-    if (seg) {
-      slot = seg->acquire(-1, &g_stop, a.lease_ms);   // blocks while every slot is with a consumer
-      if (slot < 0) break;
+    bool planar = false;
+    sim::Scene scene;         // T > 1: the pose to draw (the main thread's scene has moved on)
+    std::optional<codec::Writer> w;
+    size_t img_off = 0;
+    uint8_t* pixels = nullptr;
+    bool delta_known = false;   // ring slot of known content, published by this producer with a known generation
+    sim::StoredRect changed;
+    bool has_mask = false;
+    uint16_t mask[blocks::kMaxBands] = {};
+    double ms = 0;
+    bool done = false;        // guarded by `mu`
+  };
+  struct RenderSet {          // one Renderer per stored layout, built when first used
+    std::unique_ptr<sim::Renderer> hwc, rgb;
+  };
+
+  // ---- front half ----
+  long long dispatched = 0;
+  const bool garbage_fault = a.fault == "garbage" && a.fault_after >= 0;
+  auto front = [&](Job& j, int slot) {
+    pose(frame);
+    j.seq = dispatched++;
+    j.frame = frame;
+    j.slot = slot;
+    j.delta_known = false, j.has_mask = false, j.changed = sim::StoredRect(), j.ms = 0, j.done = false;
+    if (T > 1) {
+      if (j.scene.boxes.empty()) j.scene = scene;   // camera, light and plane never change
+      else j.scene.boxes = scene.boxes;
     }
     // this frame's layout: rgb_a when the ring's consumers all read RGB in
     // place (the hint is re-read every frame: consumers come and go)
-    bool planar = false;
+    j.planar = false;
     if (seg && !tiled && planar_ok && a.shm_layout != "interleaved")
-      planar = a.shm_layout == "planar" || (seg->hint() & 3u) == shm::kWantPlanarAlpha;
-    uint32_t gen = 0;
-    codec::Writer w(4, g_pool.take());
+      j.planar = a.shm_layout == "planar" || (seg->hint() & 3u) == shm::kWantPlanarAlpha;
+    j.w.emplace(4, g_pool.take());
+    codec::Writer& w = *j.w;
     w.begin_dict();
     w.key("btid");
     w.integer(a.btid);
-    size_t img_off = 0;
+    j.img_off = 0;
     if (!seg) {
       w.key("image");
-      img_off = w.ndarray("u1", {H, W, C}, nullptr, 64);   // 64-byte aligned payload: zero-copy GPU reads
+      j.img_off = w.ndarray("u1", {H, W, C}, nullptr, 64);   // 64-byte aligned payload: zero-copy GPU reads
     }
     w.key("xy");
     std::vector<double> xy;
@@ -427,76 +499,105 @@ int main(int argc, char** argv) {
     w.integer(frame);
     if (a.stamp) {
       w.key("seq");
-      w.integer(published);
+      w.integer(j.seq);
     }
     if (lower_left) {
       w.key("origin");
       w.str("lower-left");
     }
-    // Render into `pixels`.  A ring frame is drawn BEFORE its descriptor is
-    // written (the descriptor reports what the render changed), an inline
-    // frame after: its pixels live in the message itself.
+    // A ring frame is drawn BEFORE its descriptor is written (the descriptor
+    // reports what the render changed), an inline frame after: its pixels
+    // live in the message itself.
+    if (seg) {
+      j.pixels = seg->slot(uint32_t(slot));
+    } else {
+      w.end_dict();
+      j.pixels = w.finish().data() + j.img_off;
+    }
+    // (a frame that goes out as garbage does not advance the scene frame)
+    if (!(garbage_fault && j.seq == a.fault_after)) frame = frame >= a.frame_end ? a.frame_start : frame + 1;
+  };
+
+  // ---- render: `s` is the pose, `rs` the calling thread's renderers ----
+  auto draw = [&](Job& j, const sim::Scene& s, RenderSet& rs) {
+    const auto r0 = std::chrono::steady_clock::now();
+    const int slot = j.slot;
+    const bool planar = j.planar;
+    uint8_t* pixels = j.pixels;
     sim::DirtyRect before;       // ring slot of known content: the rectangle its last frame left
-    bool delta_known = false;    // ... and this producer knows the generation that content was published with
-    sim::StoredRect changed;
-    auto draw = [&](uint8_t* pixels) {
-      sim::DirtyRect* dirty = tiled ? &tiled_dirty : (seg && incremental ? &slot_dirty[size_t(slot)] : nullptr);
-      uint8_t* const slot_bytes = pixels;
-      if (tiled) pixels = tiled_frame.data();
-      if (seg && !tiled) {
-        uint8_t& held = slot_layout[size_t(slot)];
-        const uint8_t now = planar ? kPlanar : kInterleaved;
-        if (held != now) {
-          slot_dirty[size_t(slot)] = sim::DirtyRect();   // unknown content: full background copy
-          if (planar) fill_alpha_plane(pixels, npix);
-          held = now;
-        }
-        // what the slot's known content is about to lose (render() restores
-        // it) -- together with what this frame leaves, all that changes
-        if (dirty && dirty->known) {
-          before.x0 = dirty->x0, before.y0 = dirty->y0, before.x1 = dirty->x1, before.y1 = dirty->y1;
-          delta_known = slot_gen[size_t(slot)] != 0;
-        }
+    sim::DirtyRect* dirty = tiled ? &tiled_dirty : (seg && incremental ? &slot_dirty[size_t(slot)] : nullptr);
+    uint8_t* const slot_bytes = pixels;
+    if (tiled) pixels = tiled_frame.data();
+    if (seg && !tiled) {
+      uint8_t& held = slot_layout[size_t(slot)];
+      const uint8_t now = planar ? kPlanar : kInterleaved;
+      if (held != now) {
+        slot_dirty[size_t(slot)] = sim::DirtyRect();   // unknown content: full background copy
+        if (planar) fill_alpha_plane(pixels, npix);
+        held = now;
       }
-      (planar ? planar_renderer() : renderer()).render(scene, pixels, dirty);
-      if (a.stamp) {
-        // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
-        // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
-        uint8_t st[16] = {'B', 'T', uint8_t(a.btid & 0xff), uint8_t((a.btid >> 8) & 0xff), 0, 0, 0, 0};
-        const uint64_t q = uint64_t(published);
-        std::memcpy(st + 8, &q, 8);
-        if (planar) {
-          // the same 16 logical HWC bytes: pixels 0..3, their alpha (bytes 3, 7,
-          // 11, 15) in the alpha plane -- rewritten every frame, never restored
-          for (int p = 0; p < 4; ++p) {
-            std::memcpy(pixels + 3 * p, st + 4 * p, 3);
-            pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
-            const int row = p / W, col = p % W;   // stored row / column of pixel p
-            if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
-          }
-        } else {
-          std::memcpy(pixels, st, sizeof(st));
-          if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+      // what the slot's known content is about to lose (render() restores
+      // it) -- together with what this frame leaves, all that changes
+      if (dirty && dirty->known) {
+        before.x0 = dirty->x0, before.y0 = dirty->y0, before.x1 = dirty->x1, before.y1 = dirty->y1;
+        j.delta_known = slot_gen[size_t(slot)] != 0;
+      }
+    }
+    std::unique_ptr<sim::Renderer>& r = planar ? rs.rgb : rs.hwc;
+    if (!r) r.reset(new sim::Renderer(s, planar ? 3 : C, lower_left));
+    r->render(s, pixels, dirty);
+    if (a.stamp) {
+      // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
+      // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
+      uint8_t st[16] = {'B', 'T', uint8_t(a.btid & 0xff), uint8_t((a.btid >> 8) & 0xff), 0, 0, 0, 0};
+      const uint64_t q = uint64_t(j.seq);
+      std::memcpy(st + 8, &q, 8);
+      if (planar) {
+        // the same 16 logical HWC bytes: pixels 0..3, their alpha (bytes 3, 7,
+        // 11, 15) in the alpha plane -- rewritten every frame, never restored
+        for (int p = 0; p < 4; ++p) {
+          std::memcpy(pixels + 3 * p, st + 4 * p, 3);
+          pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
+          const int row = p / W, col = p % W;   // stored row / column of pixel p
+          if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
         }
+      } else {
+        std::memcpy(pixels, st, sizeof(st));
+        if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
       }
-      if (tiled) {
-        // everything outside this frame's dirty rectangle is background
-        if (tiled_dirty.empty())
-          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, 0, -1, 0, -1, slot_bytes);
-        else if (lower_left)   // DirtyRect rows are image rows (0 = top); stored rows are flipped
-          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, H - 1 - tiled_dirty.y1, H - 1 - tiled_dirty.y0,
-                            tiled_dirty.x0, tiled_dirty.x1, slot_bytes);
-        else
-          tiledelta::encode(pixels, key_seg->slot(0), H, W, C, tiled_dirty.y0, tiled_dirty.y1, tiled_dirty.x0,
-                            tiled_dirty.x1, slot_bytes);
-      }
-      if (delta_known) changed = sim::changed_rect(before, *dirty, H, lower_left);
-    };
-    auto r0 = std::chrono::steady_clock::now();
-    if (seg) draw(seg->slot(uint32_t(slot)));
+    }
+    if (tiled) {
+      // everything outside this frame's dirty rectangle is background
+      if (tiled_dirty.empty())
+        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, 0, -1, 0, -1, slot_bytes);
+      else if (lower_left)   // DirtyRect rows are image rows (0 = top); stored rows are flipped
+        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, H - 1 - tiled_dirty.y1, H - 1 - tiled_dirty.y0,
+                          tiled_dirty.x0, tiled_dirty.x1, slot_bytes);
+      else
+        tiledelta::encode(pixels, key_seg->slot(0), H, W, C, tiled_dirty.y0, tiled_dirty.y1, tiled_dirty.x0,
+                          tiled_dirty.x1, slot_bytes);
+    }
+    if (j.delta_known) j.changed = sim::changed_rect(before, *dirty, H, lower_left);
+    if (blocks_ok && dirty) {
+      // the blocks of this frame's spans (the stamp's pixels among them); what
+      // changed lies in those and in the ones the slot's last frame left
+      uint16_t cur[blocks::kMaxBands] = {};
+      sim::span_blocks(*dirty, H, lower_left, band_log2, cur);
+      uint16_t* prev = &slot_mask[size_t(slot) * size_t(nbands)];
+      for (int k = 0; k < nbands; ++k) j.mask[k] = uint16_t(prev[k] | cur[k]), prev[k] = cur[k];
+      j.has_mask = j.delta_known;
+    }
+    j.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
+  };
+
+  // ---- retire: false ends the stream ----
+  auto retire = [&](Job& j) -> bool {
+    const auto r0 = std::chrono::steady_clock::now();
+    const int slot = j.slot;
+    codec::Writer& w = *j.w;
     if (seg) {
       // descriptor: (segment, slot, byte offset, H, W, C, image key, generation)
-      gen = ((seg->state(uint32_t(slot)) >> 2) + 1) & 0x3fffffffu;   // publish() will bump to this
+      const uint32_t gen = ((seg->state(uint32_t(slot)) >> 2) + 1) & 0x3fffffffu;   // publish() will bump to this
       w.key("_btshm");
       w.begin_tuple();
       w.str(seg->name());
@@ -513,7 +614,7 @@ int main(int argc, char** argv) {
         w.str(key_seg->name());
         w.integer(int64_t(key_seg->state(0) >> 2));
         w.end_tuple();
-      } else if (planar) {   // 9th element: (layout,)
+      } else if (j.planar) {   // 9th element: (layout,)
         w.begin_tuple();
         w.str(planar::kName);
         w.end_tuple();
@@ -521,8 +622,10 @@ int main(int argc, char** argv) {
       // 10th element (base_gen, y0, y1, x0, x1) for a consumer that keeps slot
       // copies (shmring.h: kWantSlotDelta); never for tile16 frames, a full
       // render or a slot whose content or layout is not the one last published
-      if (!tiled && delta_known && (seg->hint() & shm::kWantSlotDelta)) {
-        if (!planar) w.none();   // interleaved frames have no 9th element: a non-tuple means "no codec"
+      const uint32_t hint = seg->hint();
+      if (!tiled && j.delta_known && (hint & shm::kWantSlotDelta)) {
+        if (!j.planar) w.none();   // interleaved frames have no 9th element: a non-tuple means "no codec"
+        const sim::StoredRect& changed = j.changed;
         w.begin_tuple();
         w.integer(slot_gen[size_t(slot)]);
         w.integer(changed.empty() ? 0 : changed.y0);
@@ -530,25 +633,31 @@ int main(int argc, char** argv) {
         w.integer(changed.empty() ? 0 : changed.x0);
         w.integer(changed.empty() ? -1 : changed.x1);
         w.end_tuple();
+        // 11th element (band_rows, mask) where the consumer asked for it
+        // (shmring.h: kWantSlotBlocks) and the frame's size allows a mask
+        if (j.has_mask && (hint & shm::kWantSlotBlocks)) {
+          uint8_t le[2 * blocks::kMaxBands];
+          for (int k = 0; k < nbands; ++k) le[2 * k] = uint8_t(j.mask[k] & 0xff), le[2 * k + 1] = uint8_t(j.mask[k] >> 8);
+          w.begin_tuple();
+          w.integer(band_rows);
+          w.bytes(le, size_t(2 * nbands));
+          w.end_tuple();
+        }
       }
       w.end_tuple();
-    }
-    w.end_dict();
-    auto& buf = w.finish();
-    uint8_t* pixels = seg ? seg->slot(uint32_t(slot)) : buf.data() + img_off;
-
-    if (!seg) draw(pixels);
-    if (seg) {
+      w.end_dict();
+      w.finish();
       seg->publish(uint32_t(slot));   // == gen
       slot_gen[size_t(slot)] = gen;
     }
-    render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
+    auto& buf = w.buffer();
+    render_ms += j.ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
 
     if (a.fault != "none" && a.fault_after >= 0 && published == a.fault_after) {
       if (a.fault == "exit") std::_Exit(3);
       if (a.fault == "stall") {
         while (!g_stop) std::this_thread::sleep_for(std::chrono::milliseconds(50));
-        break;
+        return false;
       }
       if (a.fault == "garbage") {
         zmtp::Message m;
@@ -556,14 +665,14 @@ int main(int argc, char** argv) {
         try {
           sock->send(std::move(m), 0, intr);
         } catch (const zmtp::Error&) {
-          break;
+          return false;
         }
         if (seg) {
           seg->release(uint32_t(slot), seg->publish(uint32_t(slot)));
           slot_gen[size_t(slot)] = 0;   // published twice: no consumer saw a generation to refer to
         }
         ++published;
-        continue;
+        return true;
       }
     }
 
@@ -572,17 +681,95 @@ int main(int argc, char** argv) {
     try {
       sock->send(std::move(msg), 0, intr);   // blocks at SNDHWM: backpressure
     } catch (const zmtp::Error& e) {
-      if (e.code == zmtp::E_INTR) break;
+      if (e.code == zmtp::E_INTR) return false;
       std::fprintf(stderr, "cubesim[%d]: send failed: %s\n", a.btid, e.what());
-      break;
+      return false;
     }
     ++published;
-    frame = frame >= a.frame_end ? a.frame_start : frame + 1;
     if (a.fps > 0) {
       next_due += std::chrono::microseconds(int64_t(1e6 / a.fps));
       std::this_thread::sleep_until(next_due);
     }
+    return true;
+  };
+
+  // ---- workers (T > 1): any idle worker takes the oldest queued frame ----
+  std::mutex mu;
+  std::condition_variable cv_work, cv_done;
+  std::deque<Job*> queue;
+  bool quit = false;
+  std::vector<std::thread> workers;
+  for (int t = 0; T > 1 && t < T; ++t)
+    workers.emplace_back([&] {
+      RenderSet rs;
+      for (;;) {
+        Job* j = nullptr;
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          cv_work.wait(lk, [&] { return quit || !queue.empty(); });
+          if (quit) return;
+          j = queue.front();
+          queue.pop_front();
+        }
+        draw(*j, j->scene, rs);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          j->done = true;
+        }
+        cv_done.notify_all();
+      }
+    });
+  RenderSet main_set;
+  main_set.hwc = std::move(renderer_hwc), main_set.rgb = std::move(renderer_rgb);
+
+  const size_t depth = T > 1 ? size_t(T) + 1 : 1;
+  std::vector<Job> jobs(depth);
+  size_t head = 0, inflight = 0;
+  bool ended = false;
+  for (;;) {
+    // (the hint is sticky and re-read every round: consumers come after the first frames)
+    const bool piped = T > 1 && (!by_rule || (seg && (seg->hint() & shm::kWantSlotDelta) != 0));
+    while (!ended && !g_stop && inflight < (piped ? depth : 1) && (a.frames < 0 || dispatched < a.frames)) {
+      int slot = -1;
+      if (seg) {
+        // blocks while every slot is with a consumer -- but never while a
+        // drawn frame waits for its retire: the consumer may need that frame
+        // before it hands a slot back
+        slot = seg->acquire(inflight ? 0 : -1, &g_stop, a.lease_ms);
+        if (slot < 0) {
+          ended = inflight == 0;
+          break;
+        }
+      }
+      Job& j = jobs[(head + inflight) % depth];
+      front(j, slot);
+      ++inflight;
+      if (piped) {
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          queue.push_back(&j);
+        }
+        cv_work.notify_one();
+      } else {
+        draw(j, scene, main_set);
+        j.done = true;
+      }
+    }
+    if (inflight == 0) break;
+    Job& j = jobs[head];
+    if (T > 1) {
+      std::unique_lock<std::mutex> lk(mu);
+      cv_done.wait(lk, [&] { return j.done; });
+    }
+    head = (head + 1) % depth, --inflight;
+    if (!retire(j)) break;
   }
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    quit = true;
+  }
+  cv_work.notify_all();
+  for (auto& t : workers) t.join();   // no render is left writing into the ring when it is unmapped
   double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   if (a.verbose)
     std::fprintf(stderr, "cubesim[%d]: %lld frames in %.2fs (%.1f fps, render %.3f ms/frame)\n", a.btid,

@@ -18,6 +18,7 @@
 #pragma once
 
 #include <array>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -121,6 +122,24 @@ inline StoredRect changed_rect(const DirtyRect& before, const DirtyRect& after, 
   r.y0 = lower_left ? H - 1 - u.y1 : u.y0;
   r.y1 = lower_left ? H - 1 - u.y0 : u.y1;
   return r;
+}
+
+// The 64-column x band_rows blocks (csrc/common/block_mask.h) that the pixels
+// a frame left over the background touch: `d`'s per-row spans (the rectangle
+// where it keeps none), OR-ed into out[ceil(H / band_rows)] in STORED rows.
+// The caller clears `out`; band_rows = 1 << band_log2, W <= 1024.  What a
+// render into a buffer of known content changed lies in the union of the
+// blocks of the record it found and of the one it left.
+inline void span_blocks(const DirtyRect& d, int H, bool lower_left, int band_log2, uint16_t* out) {
+  if (d.empty()) return;
+  const bool rows = d.lo.size() == std::size_t(H) && d.hi.size() == std::size_t(H);
+  const int y0 = d.y0 < 0 ? 0 : d.y0, y1 = d.y1 > H - 1 ? H - 1 : d.y1;
+  for (int y = y0; y <= y1; ++y) {
+    const int a = rows ? d.lo[std::size_t(y)] : d.x0, b = rows ? d.hi[std::size_t(y)] : d.x1;
+    if (a > b || a < 0) continue;
+    const int sy = lower_left ? H - 1 - y : y;
+    out[sy >> band_log2] |= uint16_t((2u << (unsigned(b) >> 6)) - (1u << (unsigned(a) >> 6)));
+  }
 }
 
 // Frame renderer.  Camera, light and ground plane are static for the life of

@@ -27,7 +27,16 @@
 // stored rows [y0, y1] x pixel columns [x0, x1] (inclusive; y1 < y0: nothing
 // changed) equals what this slot held when it was published with generation
 // base_gen.  A producer that does not know (the Python publisher, a slot of
-// unknown content, tile16) leaves the element out.
+// unknown content, tile16) leaves the element out.  kWantSlotBlocks: such a
+// consumer also takes a finer report, and a producer that sends element 10
+// appends descriptor element 11 = (band_rows, mask): `mask` is a bytes object
+// of ceil(H / band_rows) little-endian uint16 words, bit c of word k covering
+// stored rows [k * band_rows, (k + 1) * band_rows) x pixel columns
+// [64c, 64c + 63] on an absolute grid (csrc/common/block_mask.h) -- every byte
+// of the frame's pixel part (the RGB part of an rgb_a slot) outside the set
+// blocks equals what the slot held at base_gen.  band_rows is a power of two;
+// the element is sent only for W % 64 == 0, W <= 1024 and at most 30 bands.
+// Without the bit, descriptors are what they were.
 // Slot word = generation << 2 | state.  States: FREE (0) -> WRITING (1,
 // producer) -> PUBLISHED (2, generation bumped) -> HELD (3, a consumer took
 // the descriptor: CAS on the exact published word) -> FREE (consumer, after
@@ -60,6 +69,7 @@ constexpr uint32_t kVersion = 2;
 constexpr uint32_t kWantPlanarAlpha = 1;
 constexpr uint32_t kNeedInterleaved = 2;
 constexpr uint32_t kWantSlotDelta = 4;
+constexpr uint32_t kWantSlotBlocks = 8;
 
 struct Header {
   uint64_t magic;

@@ -366,6 +366,7 @@ class DeviceLoader:
             'staged_frames': s.get('staged_frames', 0),
             'planar_frames': s.get('planar_frames', 0),
             'delta_frames': s.get('delta_frames', 0),
+            'block_frames': s.get('block_frames', 0),
             'consumer_wait_s': self._wait_s,
             'bad': s['bad'], 'shm_stale': s['shm_stale'], 'shm_torn': s['shm_torn'],
             'pool_fallbacks': s['pool_fallbacks'],

@@ -11,6 +11,12 @@ re-interleaves into the same ``H x W x 4`` array.  A 10th element ``(base_gen,
 y0, y1, x0, x1)`` (9th then ``None`` for raw frames) is sent while a consumer set
 ``WANT_SLOT_DELTA``: all bytes outside stored rows [y0, y1] x columns [x0, x1]
 equal the slot's content at generation ``base_gen``; :func:`resolve` ignores it.
+While a consumer also set ``WANT_SLOT_BLOCKS`` an 11th element ``(band_rows,
+mask)`` follows: ``mask`` holds one little-endian uint16 per band of
+``band_rows`` stored rows, bit ``c`` of word ``k`` covering rows [k * band_rows,
+(k + 1) * band_rows) x columns [64c, 64c + 63]; all bytes of the pixel part
+outside the set blocks equal the slot's content at ``base_gen`` (sent only for
+W % 64 == 0, W <= 1024).  :func:`resolve` ignores it too.
 The GPU loader DMAs the
 slot in place; CPU consumers call :func:`resolve`, which copies the image into
 the dict under ``key`` and hands the slot back.  :class:`ShmRing` is the
@@ -46,6 +52,7 @@ _HDR = struct.Struct('<QIIQQII')
 _HINT_WORD = 8            # index of the hint among the header's u32 words
 WANT_PLANAR_ALPHA, NEED_INTERLEAVED = 1, 2    # csrc/transport/shmring.h hint bits
 WANT_SLOT_DELTA = 4
+WANT_SLOT_BLOCKS = 8
 FREE, WRITING, PUBLISHED, HELD = 0, 1, 2, 3
 HELD_LEASE_FACTOR = 20    # csrc/transport/shmring.h kHeldLeaseFactor
 KEY = '_btshm'
