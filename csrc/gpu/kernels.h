@@ -167,7 +167,7 @@ bool decode_delta_supported(const DecodeParams& p);
 hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t stream);
 
 // decode_delta() with a block mask per image in place of a rectangle (csrc/
-// common/block_mask.h): every image is cut into blocks of 64 pixel columns x
+// common/block_mask.h; the same kernel body, another inside test): every image is cut into blocks of 64 pixel columns x
 // band_rows stored rows on an absolute grid; bit c of mask[b][k] set means
 // the block in band k (stored rows [k * band_rows, (k + 1) * band_rows),
 // the last band may be partial), columns [64c, 64c + 63], comes from

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -33,6 +34,22 @@ namespace gpu {
 namespace {
 
 constexpr int kBlock = 256;
+
+// Pixels per lane (every plane store is 16 bytes) and bytes per output element.
+constexpr int ppt_for(int out) { return out == OUT_F32 ? 4 : (out == OUT_U8 ? 16 : 8); }
+constexpr int elem_for(int out) { return out == OUT_F32 ? 4 : (out == OUT_U8 ? 1 : 2); }
+
+// f(std::integral_constant<int, OUT_...>{}) for the runtime out_dtype.
+template <typename F>
+hipError_t with_out_dtype(int out_dtype, F&& f) {
+  switch (out_dtype) {
+    case OUT_F32: return f(std::integral_constant<int, OUT_F32>{});
+    case OUT_BF16: return f(std::integral_constant<int, OUT_BF16>{});
+    case OUT_F16: return f(std::integral_constant<int, OUT_F16>{});
+    case OUT_U8: return f(std::integral_constant<int, OUT_U8>{});
+  }
+  return hipErrorInvalidValue;
+}
 
 __device__ __forceinline__ uint16_t f2bf(float f) {
   // round-to-nearest-even in one v_cvt_pk_bf16_f32 (gfx950)
@@ -670,42 +687,22 @@ __device__ __forceinline__ void store_pixels(uint8_t* p, const Pixels<PPT, CIN>&
   }
 }
 
-template <int PPT, int CIN, int OUTT, int LAYOUT>
-__global__ __launch_bounds__(kBlock) void decode_delta_kernel(DecodeParams p, DeltaParams d) {
-  __shared__ uint32_t tab[kTabWords];
-  const Xf xf = stage_xf(p.lut, tab, p.Cout);
-  __syncthreads();
+// The inside test is a policy: Args travels beside DecodeParams as a kernel
+// argument, stage() fills kLdsWords words of LDS before the block's barrier,
+// inside() says whether the group at stored row sy, column x of image b is
+// read from the host.
 
-  const int64_t HW = int64_t(p.H) * p.W;
-  const int64_t groups_per_img = HW / PPT;
-  const int64_t total = groups_per_img * p.B;
-  const int cout = p.Cout;
-  int cm[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) cm[c] = p.cmap[c];
-  const int64_t stride = int64_t(gridDim.x) * kBlock;
-  const bool small = total + stride < (int64_t(1) << 31) && HW < (int64_t(1) << 31);
-
-  for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total; g += stride) {
-    Group gr;
-    int y, x;
-    split_group<PPT>(g, groups_per_img, p.W, small, gr.b, gr.q, y, x);
-    const int b = gr.b;
-    const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
-    const int64_t off = (int64_t(sy) * p.W + x) * CIN;
-    uint8_t* mir = d.mirror[b];
-    const bool inside = mir == nullptr || (sy >= int(d.y0[b]) && sy <= int(d.y1[b]) && x >= int(d.x0[b]) && x <= int(d.x1[b]));
-    const uint8_t* base = inside ? p.srcs[b] : mir;
-    gr.src = base + off;
-    Pixels<PPT, CIN> px;
-    load_pixels<PPT, CIN>(gr.src, px);
-    if (inside && mir != nullptr) store_pixels<PPT, CIN>(mir + off, px);
-    emit<PPT, CIN, OUTT, LAYOUT>(p, xf, cm, cout, HW, gr, px);
+// decode_delta: the rectangle [y0, y1] x [x0, x1] of DeltaParams.
+struct RectTest {
+  using Args = DeltaParams;
+  static constexpr int kLdsWords = 0;
+  __device__ __forceinline__ static void stage(const Args&, int, uint32_t*) {}
+  __device__ __forceinline__ static bool inside(const Args& d, const uint32_t*, int b, int sy, int x) {
+    return sy >= int(d.y0[b]) && sy <= int(d.y1[b]) && x >= int(d.x0[b]) && x <= int(d.x1[b]);
   }
-}
+};
 
-// decode_delta_kernel with a block mask as the inside test (kernels.h:
-// decode_delta_blocks): band sy >> log2(band_rows), column block x >> 6, one
+// decode_delta_blocks: band sy >> log2(band_rows), column block x >> 6, one
 // bit.  Blocks are 64 pixels wide on an absolute grid and W % 64 == 0, so a
 // group (PPT <= 16 pixels of one row, W % PPT == 0) never straddles one.  The
 // masks arrive in the kernel arguments and are staged to LDS beside the value
@@ -719,17 +716,27 @@ struct BlockArgs {
 static_assert(kMaxBlockBands <= kBlockRowWords, "a row holds the band words");
 static_assert(sizeof(DecodeParams) + sizeof(BlockArgs) <= 4096, "both structs travel as kernel arguments");
 
-template <int PPT, int CIN, int OUTT, int LAYOUT>
-__global__ __launch_bounds__(kBlock) void decode_delta_blocks_kernel(DecodeParams p, BlockArgs d) {
-  __shared__ uint32_t tab[kTabWords];
-  __shared__ uint32_t msk[kMaxBlockImgs * kBlockRowWords / 2];
-  const Xf xf = stage_xf(p.lut, tab, p.Cout);
-  {
+struct BlockTest {
+  using Args = BlockArgs;
+  static constexpr int kLdsWords = kMaxBlockImgs * kBlockRowWords / 2;
+  __device__ __forceinline__ static void stage(const Args& d, int B, uint32_t* msk) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&d.rows[0][0]);
-    for (int i = threadIdx.x; i < p.B * (kBlockRowWords / 2); i += kBlock) msk[i] = src[i];
+    for (int i = threadIdx.x; i < B * (kBlockRowWords / 2); i += kBlock) msk[i] = src[i];
   }
+  __device__ __forceinline__ static bool inside(const Args& d, const uint32_t* msk, int b, int sy, int x) {
+    const uint16_t* rows = reinterpret_cast<const uint16_t*>(msk);
+    const uint32_t word = rows[b * kBlockRowWords + (sy >> d.band_log2)];   // (band < kMaxBlockBands: checked on the host)
+    return ((word >> (x >> 6)) & 1u) != 0;
+  }
+};
+
+template <int PPT, int CIN, int OUTT, int LAYOUT, typename Test>
+__global__ __launch_bounds__(kBlock) void decode_mirror_kernel(DecodeParams p, typename Test::Args d) {
+  __shared__ uint32_t tab[kTabWords];
+  __shared__ uint32_t msk[Test::kLdsWords > 0 ? Test::kLdsWords : 1];
+  const Xf xf = stage_xf(p.lut, tab, p.Cout);
+  Test::stage(d, p.B, msk);
   __syncthreads();
-  const uint16_t* rows = reinterpret_cast<const uint16_t*>(msk);
 
   const int64_t HW = int64_t(p.H) * p.W;
   const int64_t groups_per_img = HW / PPT;
@@ -749,8 +756,7 @@ __global__ __launch_bounds__(kBlock) void decode_delta_blocks_kernel(DecodeParam
     const int sy = image_flipped(p, b) ? p.H - 1 - y : y;
     const int64_t off = (int64_t(sy) * p.W + x) * CIN;
     uint8_t* mir = d.mirror[b];
-    const uint32_t word = rows[b * kBlockRowWords + (sy >> d.band_log2)];   // (band < kMaxBlockBands: checked on the host)
-    const bool inside = mir == nullptr || ((word >> (x >> 6)) & 1u) != 0;
+    const bool inside = mir == nullptr || Test::inside(d, msk, b, sy, x);
     const uint8_t* base = inside ? p.srcs[b] : mir;
     gr.src = base + off;
     Pixels<PPT, CIN> px;
@@ -813,7 +819,7 @@ hipError_t launch_vec(const DecodeParams& p, hipStream_t s) {
 
 template <int OUTT>
 hipError_t launch_out(const DecodeParams& p, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int PPT = ppt_for(OUTT);
   // vector path: a lane's PPT pixels sit in one row and its loads are aligned
   const bool src_aligned = p.nsrcs ? srcs_ok(p.srcs, p.nsrcs, p.B, 16)
                                    : (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 && (p.src_offsets == nullptr || p.src_offsets_aligned);
@@ -846,7 +852,7 @@ void launch_tiles(const DecodeParams& p, const TileParams& t, int grid, hipStrea
 
 template <int OUTT>
 void launch_tiles_out(const DecodeParams& p, const TileParams& t, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int PPT = ppt_for(OUTT);
   const int64_t work = int64_t(t.tile_start[p.B]) * (256 / PPT);
   if (work <= 0) return;
   const int grid = grid_for(work, p.max_grid);
@@ -863,13 +869,7 @@ hipError_t decode(const DecodeParams& p, hipStream_t stream) {
   if (p.ndsts && (p.ndsts != p.B || p.ndsts > kMaxSrcs || !dsts_ok(p.dsts, p.ndsts, p.B, 1))) return hipErrorInvalidValue;
   for (int c = 0; c < p.Cout; ++c)
     if (p.cmap[c] < 0 || p.cmap[c] >= p.Cin) return hipErrorInvalidValue;
-  switch (p.out_dtype) {
-    case OUT_F32: return launch_out<OUT_F32>(p, stream);
-    case OUT_BF16: return launch_out<OUT_BF16>(p, stream);
-    case OUT_F16: return launch_out<OUT_F16>(p, stream);
-    case OUT_U8: return launch_out<OUT_U8>(p, stream);
-  }
-  return hipErrorInvalidValue;
+  return with_out_dtype(p.out_dtype, [&](auto o) { return launch_out<o()>(p, stream); });
 }
 
 namespace {
@@ -885,8 +885,8 @@ void launch_crop_vec(const DecodeParams& p, const CropParams& c, hipStream_t s) 
 
 template <int OUTT>
 hipError_t launch_crop_out(const DecodeParams& p, const CropParams& c, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
-  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  constexpr int PPT = ppt_for(OUTT);
+  constexpr int64_t ELEM = elem_for(OUTT);
   // vector path: a lane's PPT pixels sit in one window row, every image's
   // source misalignment is a whole number of bytes below a dword of a
   // 16-byte aligned frame whose rows are dword multiples, and the 16-byte
@@ -923,13 +923,7 @@ hipError_t decode_crop(const DecodeParams& p, const CropParams& c, hipStream_t s
   for (int k = 0; k < p.Cout; ++k)
     if (p.cmap[k] < 0 || p.cmap[k] >= p.Cin) return hipErrorInvalidValue;
   if (p.B == 0) return hipSuccess;
-  switch (p.out_dtype) {
-    case OUT_F32: return launch_crop_out<OUT_F32>(p, c, stream);
-    case OUT_BF16: return launch_crop_out<OUT_BF16>(p, c, stream);
-    case OUT_F16: return launch_crop_out<OUT_F16>(p, c, stream);
-    case OUT_U8: return launch_crop_out<OUT_U8>(p, c, stream);
-  }
-  return hipErrorInvalidValue;
+  return with_out_dtype(p.out_dtype, [&](auto o) { return launch_crop_out<o()>(p, c, stream); });
 }
 
 // ---- resized crop (kernels.h: decode_resize) -------------------------------
@@ -1256,8 +1250,8 @@ void launch_resize_vec(const DecodeParams& p, const ResizeParams& r, int R, int 
 
 template <int OUTT>
 hipError_t launch_resize_out(const DecodeParams& p, const ResizeParams& r, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
-  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  constexpr int PPT = ppt_for(OUTT);
+  constexpr int64_t ELEM = elem_for(OUTT);
   // staged path: decode_crop's conditions on the sources (16-byte aligned
   // frames; packed RGB rows a whole number of dwords) and on the stores
   const bool src_aligned = p.nsrcs ? srcs_ok(p.srcs, p.nsrcs, p.B, 16)
@@ -1301,45 +1295,37 @@ hipError_t decode_resize(const DecodeParams& p, const ResizeParams& r, hipStream
   for (int k = 0; k < p.Cout; ++k)
     if (p.cmap[k] < 0 || p.cmap[k] >= p.Cin) return hipErrorInvalidValue;
   if (p.B == 0) return hipSuccess;
-  switch (p.out_dtype) {
-    case OUT_F32: return launch_resize_out<OUT_F32>(p, r, stream);
-    case OUT_BF16: return launch_resize_out<OUT_BF16>(p, r, stream);
-    case OUT_F16: return launch_resize_out<OUT_F16>(p, r, stream);
-    case OUT_U8: return launch_resize_out<OUT_U8>(p, r, stream);
-  }
-  return hipErrorInvalidValue;
+  return with_out_dtype(p.out_dtype, [&](auto o) { return launch_resize_out<o()>(p, r, stream); });
 }
 
 namespace {
 
-constexpr int delta_ppt(int out_dtype) { return out_dtype == OUT_F32 ? 4 : (out_dtype == OUT_U8 ? 16 : 8); }
-
-template <int OUTT>
-hipError_t launch_delta_out(const DecodeParams& p, const DeltaParams& d, hipStream_t s) {
-  constexpr int PPT = delta_ppt(OUTT);
+template <int OUTT, typename Test>
+hipError_t launch_mirror_out(const DecodeParams& p, const typename Test::Args& d, hipStream_t s) {
+  constexpr int PPT = ppt_for(OUTT);
   const int grid = grid_for(int64_t(p.B) * p.H * p.W / PPT, p.max_grid);
   if (p.Cin == 4) {
-    if (p.layout == NCHW) decode_delta_kernel<PPT, 4, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
-    else decode_delta_kernel<PPT, 4, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+    if (p.layout == NCHW) decode_mirror_kernel<PPT, 4, OUTT, NCHW, Test><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_mirror_kernel<PPT, 4, OUTT, NHWC, Test><<<grid, kBlock, 0, s>>>(p, d);
   } else {
-    if (p.layout == NCHW) decode_delta_kernel<PPT, 3, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
-    else decode_delta_kernel<PPT, 3, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
+    if (p.layout == NCHW) decode_mirror_kernel<PPT, 3, OUTT, NCHW, Test><<<grid, kBlock, 0, s>>>(p, d);
+    else decode_mirror_kernel<PPT, 3, OUTT, NHWC, Test><<<grid, kBlock, 0, s>>>(p, d);
   }
   return hipGetLastError();
 }
 
-template <int OUTT>
-hipError_t launch_blocks_out(const DecodeParams& p, const BlockArgs& d, hipStream_t s) {
-  constexpr int PPT = delta_ppt(OUTT);
-  const int grid = grid_for(int64_t(p.B) * p.H * p.W / PPT, p.max_grid);
-  if (p.Cin == 4) {
-    if (p.layout == NCHW) decode_delta_blocks_kernel<PPT, 4, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
-    else decode_delta_blocks_kernel<PPT, 4, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
-  } else {
-    if (p.layout == NCHW) decode_delta_blocks_kernel<PPT, 3, OUTT, NCHW><<<grid, kBlock, 0, s>>>(p, d);
-    else decode_delta_blocks_kernel<PPT, 3, OUTT, NHWC><<<grid, kBlock, 0, s>>>(p, d);
-  }
-  return hipGetLastError();
+template <typename Test>
+hipError_t launch_mirror(const DecodeParams& p, const typename Test::Args& d, hipStream_t s) {
+  return with_out_dtype(p.out_dtype, [&](auto o) { return launch_mirror_out<o(), Test>(p, d, s); });
+}
+
+// what both mirror reads ask beyond decode_delta_supported(): a dense output
+// whose images are 16-byte multiples, and 16-byte aligned mirrors
+bool mirror_buffers_ok(const DecodeParams& p, uint8_t* const* mirror) {
+  if (!p.ndsts && (size_t(p.H) * p.W * p.Cout * size_t(elem_for(p.out_dtype))) % 16 != 0) return false;
+  for (int b = 0; b < p.B; ++b)
+    if ((reinterpret_cast<uintptr_t>(mirror[b]) % 16) != 0) return false;
+  return true;
 }
 
 }  // namespace
@@ -1351,7 +1337,7 @@ bool decode_delta_supported(const DecodeParams& p) {
   if (p.out_dtype < OUT_F32 || p.out_dtype > OUT_U8 || (p.layout != NCHW && p.layout != NHWC)) return false;
   for (int c = 0; c < p.Cout; ++c)
     if (p.cmap[c] < 0 || p.cmap[c] >= p.Cin) return false;
-  if (p.W % delta_ppt(p.out_dtype) != 0 || (int64_t(p.H) * p.W * p.Cin) % 16 != 0) return false;
+  if (p.W % ppt_for(p.out_dtype) != 0 || (int64_t(p.H) * p.W * p.Cin) % 16 != 0) return false;
   if (!srcs_ok(p.srcs, p.nsrcs, p.B, 16)) return false;
   return p.ndsts ? dsts_ok(p.dsts, p.ndsts, p.B, 16) : p.dst != nullptr && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0;
 }
@@ -1359,12 +1345,9 @@ bool decode_delta_supported(const DecodeParams& p) {
 hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t stream) {
   // every condition is checked here, before anything is launched
   if (p.B == 0) return hipSuccess;
-  if (!decode_delta_supported(p)) return hipErrorInvalidValue;
-  const size_t elem = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 1 : 2);
-  if (!p.ndsts && (size_t(p.H) * p.W * p.Cout * elem) % 16 != 0) return hipErrorInvalidValue;
+  if (!decode_delta_supported(p) || !mirror_buffers_ok(p, d.mirror)) return hipErrorInvalidValue;
   for (int b = 0; b < p.B; ++b) {
     if (!d.mirror[b]) continue;
-    if ((reinterpret_cast<uintptr_t>(d.mirror[b]) % 16) != 0) return hipErrorInvalidValue;
     const int y0 = d.y0[b], y1 = d.y1[b], x0 = d.x0[b], x1 = d.x1[b];
     if (y1 < y0) continue;   // nothing from the host
     if (y0 < 0 || y1 >= p.H || x0 < 0 || x1 < x0 || x1 >= p.W) return hipErrorInvalidValue;
@@ -1372,13 +1355,7 @@ hipError_t decode_delta(const DecodeParams& p, const DeltaParams& d, hipStream_t
     const bool blocks = x0 % 64 == 0 && ((x1 + 1) % 64 == 0 || x1 == p.W - 1) && p.W % 64 == 0;
     if (!full_rows && !blocks) return hipErrorInvalidValue;
   }
-  switch (p.out_dtype) {
-    case OUT_F32: return launch_delta_out<OUT_F32>(p, d, stream);
-    case OUT_BF16: return launch_delta_out<OUT_BF16>(p, d, stream);
-    case OUT_F16: return launch_delta_out<OUT_F16>(p, d, stream);
-    case OUT_U8: return launch_delta_out<OUT_U8>(p, d, stream);
-  }
-  return hipErrorInvalidValue;
+  return launch_mirror<RectTest>(p, d, stream);
 }
 
 bool decode_delta_blocks_supported(const DecodeParams& p) {
@@ -1388,9 +1365,7 @@ bool decode_delta_blocks_supported(const DecodeParams& p) {
 hipError_t decode_delta_blocks(const DecodeParams& p, const BlockParams& d, hipStream_t stream) {
   // every condition is checked here, before anything is launched
   if (p.B == 0) return hipSuccess;
-  if (!decode_delta_blocks_supported(p)) return hipErrorInvalidValue;
-  const size_t elem = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 1 : 2);
-  if (!p.ndsts && (size_t(p.H) * p.W * p.Cout * elem) % 16 != 0) return hipErrorInvalidValue;
+  if (!decode_delta_blocks_supported(p) || !mirror_buffers_ok(p, d.mirror)) return hipErrorInvalidValue;
   BlockArgs a = {};
   const unsigned cols = (2u << unsigned((p.W - 1) / 64)) - 1u;
   const int br = d.band_rows;
@@ -1401,26 +1376,19 @@ hipError_t decode_delta_blocks(const DecodeParams& p, const BlockParams& d, hipS
   for (int b = 0; b < p.B; ++b) {
     a.mirror[b] = d.mirror[b];
     if (!d.mirror[b]) continue;
-    if ((reinterpret_cast<uintptr_t>(d.mirror[b]) % 16) != 0) return hipErrorInvalidValue;
     for (int k = 0; k < kMaxBlockBands; ++k) {
       const unsigned w = d.mask[b][k];
       if (k >= nb ? w != 0 : (w & ~cols) != 0) return hipErrorInvalidValue;   // a bit outside the frame
       a.rows[b][k] = uint16_t(w);
     }
   }
-  switch (p.out_dtype) {
-    case OUT_F32: return launch_blocks_out<OUT_F32>(p, a, stream);
-    case OUT_BF16: return launch_blocks_out<OUT_BF16>(p, a, stream);
-    case OUT_F16: return launch_blocks_out<OUT_F16>(p, a, stream);
-    case OUT_U8: return launch_blocks_out<OUT_U8>(p, a, stream);
-  }
-  return hipErrorInvalidValue;
+  return launch_mirror<BlockTest>(p, a, stream);
 }
 
 hipError_t decode_tiles(const DecodeParams& p, const TileParams& t, hipStream_t stream) {
   if (p.B <= 0) return hipSuccess;
-  const int ppt = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 16 : 8);
-  const size_t elem = p.out_dtype == OUT_F32 ? 4 : (p.out_dtype == OUT_U8 ? 1 : 2);
+  const int ppt = ppt_for(p.out_dtype);
+  const size_t elem = elem_for(p.out_dtype);
   if (p.B > kMaxSrcs || p.nsrcs != p.B || p.H % 16 != 0 || p.W % 16 != 0 || (p.Cin != 3 && p.Cin != 4) ||
       p.Cout < 1 || p.Cout > 4 || p.W % ppt != 0 || t.payload_off % 16 != 0 || t.out_img_bytes % 16 != 0 ||
       t.out_img_bytes != int64_t(p.H) * p.W * p.Cout * int64_t(elem) || !srcs_ok(p.srcs, p.nsrcs, p.B, 16) ||
@@ -1436,14 +1404,10 @@ hipError_t decode_tiles(const DecodeParams& p, const TileParams& t, hipStream_t 
     if (p.cmap[c] < 0 || p.cmap[c] >= p.Cin) return hipErrorInvalidValue;
   const int64_t chunks = t.out_img_bytes / 16 * p.B;
   tile_fill_kernel<<<grid_for(chunks, 0), kBlock, 0, stream>>>(p, t);
-  switch (p.out_dtype) {
-    case OUT_F32: launch_tiles_out<OUT_F32>(p, t, stream); break;
-    case OUT_BF16: launch_tiles_out<OUT_BF16>(p, t, stream); break;
-    case OUT_F16: launch_tiles_out<OUT_F16>(p, t, stream); break;
-    case OUT_U8: launch_tiles_out<OUT_U8>(p, t, stream); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_out_dtype(p.out_dtype, [&](auto o) {
+    launch_tiles_out<o()>(p, t, stream);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1663,7 +1627,7 @@ __global__ __launch_bounds__(kBlock) void replay_scalar_kernel(DecodeParams p, R
 
 template <int OUTT>
 hipError_t launch_replay(const DecodeParams& p, const ReplayParams& r, int64_t meta_units, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
+  constexpr int PPT = ppt_for(OUTT);
   const bool vec = (p.W % PPT) == 0 && r.frame_bytes % 16 == 0 && (p.Cin == 3 || p.Cin == 4) &&
                    (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0 &&
                    (int64_t(p.H) * p.W * p.Cin) % 16 == 0;
@@ -1724,13 +1688,7 @@ hipError_t replay_sample(const DecodeParams& p, const ReplayParams& r, hipStream
       return hipErrorInvalidValue;
     meta_units += int64_t(p.B) * (nb % 4 == 0 ? nb / 4 : nb);
   }
-  hipError_t e = hipErrorInvalidValue;
-  switch (p.out_dtype) {
-    case OUT_F32: e = launch_replay<OUT_F32>(p, r, meta_units, stream); break;
-    case OUT_BF16: e = launch_replay<OUT_BF16>(p, r, meta_units, stream); break;
-    case OUT_F16: e = launch_replay<OUT_F16>(p, r, meta_units, stream); break;
-    case OUT_U8: e = launch_replay<OUT_U8>(p, r, meta_units, stream); break;
-  }
+  const hipError_t e = with_out_dtype(p.out_dtype, [&](auto o) { return launch_replay<o()>(p, r, meta_units, stream); });
   if (e != hipSuccess || r.index_in || !r.counter) return e;
   replay_advance_kernel<<<1, 1, 0, stream>>>(r.counter, p.B);
   return hipGetLastError();
@@ -1974,8 +1932,8 @@ void launch_replay_crop_vec(const DecodeParams& p, const ReplayParams& r, const 
 template <int OUTT>
 hipError_t launch_replay_crop(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                               int64_t meta_units, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
-  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  constexpr int PPT = ppt_for(OUTT);
+  constexpr int64_t ELEM = elem_for(OUTT);
   // decode_crop's vector conditions on replay's dense store and output
   const bool vec = (c.w % PPT) == 0 && (p.W % 4) == 0 && r.frame_bytes % 16 == 0 && (p.Cin == 3 || p.Cin == 4) &&
                    (reinterpret_cast<uintptr_t>(p.src) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.dst) % 16) == 0 &&
@@ -2032,13 +1990,8 @@ hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, cons
   if (p.B == 0) return hipSuccess;
   c.ny = uint32_t(p.H + 2 * c.pad - c.h + 1);
   c.nx = uint32_t((p.W + 2 * c.pad - c.w) / c.x_align + 1);
-  hipError_t e = hipErrorInvalidValue;
-  switch (p.out_dtype) {
-    case OUT_F32: e = launch_replay_crop<OUT_F32>(p, r, c, meta_units, stream); break;
-    case OUT_BF16: e = launch_replay_crop<OUT_BF16>(p, r, c, meta_units, stream); break;
-    case OUT_F16: e = launch_replay_crop<OUT_F16>(p, r, c, meta_units, stream); break;
-    case OUT_U8: e = launch_replay_crop<OUT_U8>(p, r, c, meta_units, stream); break;
-  }
+  const hipError_t e =
+      with_out_dtype(p.out_dtype, [&](auto o) { return launch_replay_crop<o()>(p, r, c, meta_units, stream); });
   // a device counter moves on when this launch drew from it: indices, or windows
   const bool drew = !r.index_in || (c.mode == kCropRandom && !c.windows_in);
   if (e != hipSuccess || !r.counter || !drew) return e;
@@ -2298,8 +2251,8 @@ void launch_replay_stack_vec(const DecodeParams& p, const ReplayParams& r, const
 template <int OUTT>
 hipError_t launch_replay_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                                const ReplayStackParams& t, int64_t meta_units, int64_t anchor_units, hipStream_t s) {
-  constexpr int PPT = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 16 : 8);
-  constexpr int64_t ELEM = OUTT == OUT_F32 ? 4 : (OUTT == OUT_U8 ? 1 : 2);
+  constexpr int PPT = ppt_for(OUTT);
+  constexpr int64_t ELEM = elem_for(OUTT);
   const size_t lds = sizeof(uint32_t) * (size_t(p.B) * size_t(t.stack + 1) + 2 * size_t(p.B));
   const int64_t pixels = int64_t(2) * p.B * t.stack * c.h * c.w;
   // launch_replay_crop's vector conditions
@@ -2373,13 +2326,8 @@ hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, con
   c.ny = uint32_t(p.H + 2 * c.pad - c.h + 1);
   c.nx = uint32_t((p.W + 2 * c.pad - c.w) / c.x_align + 1);
   const int64_t meta_units = anchor_units + next_units;
-  hipError_t e = hipErrorInvalidValue;
-  switch (p.out_dtype) {
-    case OUT_F32: e = launch_replay_stack<OUT_F32>(p, r, c, t, meta_units, anchor_units, stream); break;
-    case OUT_BF16: e = launch_replay_stack<OUT_BF16>(p, r, c, t, meta_units, anchor_units, stream); break;
-    case OUT_F16: e = launch_replay_stack<OUT_F16>(p, r, c, t, meta_units, anchor_units, stream); break;
-    case OUT_U8: e = launch_replay_stack<OUT_U8>(p, r, c, t, meta_units, anchor_units, stream); break;
-  }
+  const hipError_t e = with_out_dtype(
+      p.out_dtype, [&](auto o) { return launch_replay_stack<o()>(p, r, c, t, meta_units, anchor_units, stream); });
   // a device counter moves on when this launch drew from it: anchors, or windows
   const bool drew = !r.index_in || c.mode == kCropRandom;
   if (e != hipSuccess || !r.counter || !drew) return e;

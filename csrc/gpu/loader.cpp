@@ -1362,6 +1362,22 @@ void StreamLoader::flush_pending(bool force) {
   pending_images_ = 0;
 }
 
+// Images [lo, lo + n) of a launch over per-image sources as a launch of their own.
+static DecodeParams slice_params(const DecodeParams& sp, size_t lo, size_t n, size_t out_img_bytes) {
+  DecodeParams part = sp;
+  if (lo == 0 && n == size_t(sp.B)) return part;
+  std::memset(part.flip_bits, 0, sizeof(part.flip_bits));
+  for (size_t i = 0; i < n; ++i) {
+    part.srcs[i] = sp.srcs[lo + i];
+    if (sp.ndsts) part.dsts[i] = sp.dsts[lo + i];
+    if ((sp.flip_bits[(lo + i) >> 6] >> ((lo + i) & 63)) & 1) part.flip_bits[i >> 6] |= uint64_t(1) << (i & 63);
+  }
+  part.B = part.nsrcs = int(n);
+  if (sp.ndsts) part.ndsts = int(n);
+  else part.dst = static_cast<uint8_t*>(sp.dst) + lo * out_img_bytes;   // one dense batch: this part's images
+  return part;
+}
+
 void StreamLoader::launch_group(std::vector<Pending>& group) {
   trace::Range tr("btn.loader.launch");
   CpuScope cpu(cpu_ns_[kCpuLaunch]);
@@ -1632,105 +1648,74 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     // Frames that admit a block grid (W % 64 == 0, W <= 1024) take
     // decode_delta_blocks whether their producer sent a mask or only a
     // rectangle (the mask is then built from the widened rectangle), at most
-    // kMaxBlockImgs images per launch; other sizes, and BT_SLOT_BLOCKS=0, keep
-    // decode_delta.
+    // kMaxBlockImgs images per launch (the masks travel in the kernel
+    // arguments); other sizes, and BT_SLOT_BLOCKS=0, keep decode_delta.
     const bool mirror_on = plain && !cfg_.crop && !cfg_.resize && mirror_wanted();
-    auto run_blocks = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
-      const size_t frame = size_t(H_) * W_ * size_t(sp.Cin);
+    // the kernel reads this image in its ring slot?  (not a frame staged or rebuilt elsewhere)
+    auto in_slot = [](const Item& it) { return it.ms && !it.staged && it.expanded.empty(); };
+    // The mirror of the slot such an image lies in; null when the kernel does
+    // not read the image there, or when the slot is not mirrored (now): then
+    // whatever the copy held for this slot is no base for a later report.
+    auto ring_mirror = [&](const Item& it, int cin, bool ok) -> uint8_t* {
+      if (!in_slot(it)) return nullptr;
+      uint8_t* m = ok ? slot_mirror(*it.ms, cin, it.has_delta) : nullptr;
+      if (!m) it.ms->ring.invalidate(it.slot);
+      return m ? m + size_t(it.slot) * size_t(H_) * W_ * size_t(cin) : nullptr;
+    };
+    auto run_mirror = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs, bool ok, bool by_blocks) {
       uint64_t saved = 0, deltas = 0, fine = 0;
       hipError_t err = hipSuccess;
-      // the masks travel in the kernel arguments: at most kMaxBlockImgs images per launch
-      for (size_t lo = 0; lo < imgs.size() && err == hipSuccess; lo += size_t(kMaxBlockImgs)) {
-        const size_t n_here = std::min(imgs.size() - lo, size_t(kMaxBlockImgs));
-        DecodeParams part = sp;
+      const size_t step = by_blocks ? size_t(kMaxBlockImgs) : imgs.size();
+      for (size_t lo = 0; lo < imgs.size() && err == hipSuccess; lo += step) {
+        const size_t n_here = std::min(imgs.size() - lo, step);
+        const DecodeParams part = slice_params(sp, lo, n_here, out_img_bytes);
+        DeltaParams dl;
         BlockParams bp;
         bp.band_rows = blocks::band_rows_for(H_);   // one grid per frame size (slot_mirror.h: decide_blocks)
-        if (lo != 0 || n_here != imgs.size()) {
-          std::memset(part.flip_bits, 0, sizeof(part.flip_bits));
-          for (size_t n = 0; n < n_here; ++n) {
-            part.srcs[n] = sp.srcs[lo + n];
-            if (sp.ndsts) part.dsts[n] = sp.dsts[lo + n];
-            if ((sp.flip_bits[(lo + n) >> 6] >> ((lo + n) & 63)) & 1) part.flip_bits[n >> 6] |= uint64_t(1) << (n & 63);
-          }
-          part.B = part.nsrcs = int(n_here);
-          if (sp.ndsts) part.ndsts = int(n_here);
-          else part.dst = static_cast<uint8_t*>(sp.dst) + lo * out_img_bytes;   // one dense batch: this part's images
-        }
+        bool any = false;
         for (size_t n = 0; n < n_here; ++n) {
           const Item& it = *imgs[lo + n];
-          // the kernel reads this image in its ring slot?  (not a frame staged or rebuilt elsewhere)
-          if (!it.ms || it.staged || !it.expanded.empty()) continue;
-          uint8_t* m = slot_mirror(*it.ms, sp.Cin, it.has_delta);
-          if (!m) {   // not mirrored (now): whatever the copy held for this slot is no base for a later report
-            it.ms->ring.invalidate(it.slot);
-            continue;
-          }
+          uint8_t* m = ring_mirror(it, sp.Cin, ok);
+          if (!m) continue;
+          const mirror::Delta* report = it.has_delta ? &it.delta : nullptr;
           bool used = false, masked = false;
-          const mirror::BlockMask bm = it.ms->ring.decide_blocks(it.slot, it.gen, it.has_delta ? &it.delta : nullptr,
-                                                                 it.has_blocks ? &it.blocks : nullptr, H_, W_, &used, &masked);
-          bp.mirror[n] = m + size_t(it.slot) * frame;
-          std::memcpy(bp.mask[n], bm.w, sizeof(bp.mask[n]));
+          int64_t host_pixels;
+          if (by_blocks) {
+            const mirror::BlockMask bm = it.ms->ring.decide_blocks(it.slot, it.gen, report, it.has_blocks ? &it.blocks : nullptr,
+                                                                   H_, W_, &used, &masked);
+            bp.mirror[n] = m;
+            std::memcpy(bp.mask[n], bm.w, sizeof(bp.mask[n]));
+            host_pixels = bm.pixels(H_);
+          } else {
+            const mirror::Region r = it.ms->ring.decide(it.slot, it.gen, report, H_, W_, &used);
+            dl.mirror[n] = m;
+            dl.y0[n] = int16_t(r.y0), dl.y1[n] = int16_t(r.y1), dl.x0[n] = int16_t(r.x0), dl.x1[n] = int16_t(r.x1);
+            host_pixels = r.pixels();
+          }
+          any = true;
           if (used) {
             deltas++;
             fine += masked;
-            saved += uint64_t(int64_t(H_) * W_ - bm.pixels(H_)) * uint64_t(sp.Cin);
+            saved += uint64_t(int64_t(H_) * W_ - host_pixels) * uint64_t(sp.Cin);
           }
         }
-        bool any = false;
-        for (size_t n = 0; n < n_here; ++n) any = any || bp.mirror[n] != nullptr;
-        err = any ? decode_delta_blocks(part, bp, st) : decode(part, st);
+        err = !any ? decode(part, st) : by_blocks ? decode_delta_blocks(part, bp, st) : decode_delta(part, dl, st);
       }
-      {
-        // only the set blocks cross the link: take back what process() counted for whole frames
-        std::lock_guard<std::mutex> lk(mu_);
-        stats_.delta_frames += deltas;
-        stats_.block_frames += fine;
-        stats_.image_bytes -= saved;
-      }
+      // only the regions or set blocks cross the link: take back what process() counted for whole frames
+      std::lock_guard<std::mutex> lk(mu_);
+      stats_.delta_frames += deltas;
+      stats_.block_frames += fine;
+      stats_.image_bytes -= saved;
       return err;
     };
     auto run_plain = [&](const DecodeParams& sp, const std::vector<const Item*>& imgs) -> hipError_t {
-      if (!mirror_on) return decode(sp, st);
+      bool any_ring = false;
+      for (const Item* it : imgs) any_ring = any_ring || in_slot(*it);
+      if (!mirror_on || !any_ring) return decode(sp, st);
       // (RGBA -> RGBA u8 NHWC keeps decode()'s 4-pixel host-read shape, kernels.hip launch_out: not mirrored)
       const bool raw_rgba = sp.out_dtype == OUT_U8 && sp.layout == NHWC && sp.Cin == 4 && sp.Cout == 4;
       const bool ok = !raw_rgba && decode_delta_supported(sp);
-      if (ok && slot_blocks_ && blocks::width_ok(W_)) {
-        bool any_ring = false;
-        for (const Item* it : imgs) any_ring = any_ring || (it->ms && !it->staged && it->expanded.empty());
-        if (any_ring) return run_blocks(sp, imgs);
-        return decode(sp, st);
-      }
-      DeltaParams dl;
-      bool any = false;
-      uint64_t saved = 0, deltas = 0;
-      const size_t frame = size_t(H_) * W_ * size_t(sp.Cin);
-      for (size_t n = 0; n < imgs.size(); ++n) {
-        const Item& it = *imgs[n];
-        // the kernel reads this image in its ring slot?  (not a frame staged or rebuilt elsewhere)
-        if (!it.ms || it.staged || !it.expanded.empty()) continue;
-        uint8_t* m = ok ? slot_mirror(*it.ms, sp.Cin, it.has_delta) : nullptr;
-        if (!m) {   // not mirrored (now): whatever the copy held for this slot is no base for a later report
-          it.ms->ring.invalidate(it.slot);
-          continue;
-        }
-        bool used = false;
-        const mirror::Region r = it.ms->ring.decide(it.slot, it.gen, it.has_delta ? &it.delta : nullptr, H_, W_, &used);
-        dl.mirror[n] = m + size_t(it.slot) * frame;
-        dl.y0[n] = int16_t(r.y0), dl.y1[n] = int16_t(r.y1), dl.x0[n] = int16_t(r.x0), dl.x1[n] = int16_t(r.x1);
-        any = true;
-        if (used) {
-          deltas++;
-          saved += uint64_t(int64_t(H_) * W_ - r.pixels()) * uint64_t(sp.Cin);
-        }
-      }
-      if (!any) return decode(sp, st);
-      {
-        // only the regions cross the link: take back what process() counted for whole frames
-        std::lock_guard<std::mutex> lk(mu_);
-        stats_.delta_frames += deltas;
-        stats_.image_bytes -= saved;
-      }
-      return decode_delta(sp, dl, st);
+      return run_mirror(sp, imgs, ok, ok && slot_blocks_ && blocks::width_ok(W_));
     };
     if (nplanar > 0 && nplanar < total) {
       // both source layouts in one group (a mixed fleet with inline

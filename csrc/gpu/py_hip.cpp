@@ -143,6 +143,19 @@ void fill_cmap(int* dst, const std::vector<int>& cmap) {
   for (size_t i = 0; i < 4; ++i) dst[i] = i < cmap.size() ? cmap[i] : int(i);
 }
 
+// The scalar fields of DecodeParams that every decode binding takes as they are.
+void fill_scalars(DecodeParams& p, uintptr_t dst, uintptr_t lut, int B, int H, int W, int Cin, int Cout,
+                  const std::vector<int>& cmap, int flip_all, int out_dtype, int layout, int max_grid) {
+  p.dst = ptr<void>(dst);
+  p.lut = ptr<const float>(lut);
+  p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+  fill_cmap(p.cmap, cmap);
+  p.flip_all = flip_all;
+  p.out_dtype = out_dtype;
+  p.layout = layout;
+  p.max_grid = max_grid;
+}
+
 // Per-image launch parameters of DecodeParams / Color4x4Params from Python lists
 // (device pointers as integers): srcs / dsts of up to kMaxSrcs entries, up to 4
 // flip_bits words.  Empty lists leave the dense src / dst form.
@@ -247,19 +260,12 @@ PYBIND11_MODULE(_hip, m) {
            std::vector<int> crop, std::vector<int> resize_size, std::vector<int> window) {
           DecodeParams p;
           fill_image_lists(p, srcs, dsts, flip_bits, "decode");
-          p.max_grid = max_grid;
+          fill_scalars(p, dst, lut, B, H, W, Cin, Cout, cmap, flip_all, out_dtype, layout, max_grid);
           p.unroll = unroll;
           p.src = ptr<const uint8_t>(src);
           p.src_offsets = ptr<const int64_t>(src_offsets);
           p.src_offsets_aligned = src_offsets_aligned;
-          p.dst = ptr<void>(dst);
-          p.lut = ptr<const float>(lut);
           p.flip = ptr<const uint8_t>(flip);
-          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
-          fill_cmap(p.cmap, cmap);
-          p.flip_all = flip_all;
-          p.out_dtype = out_dtype;
-          p.layout = layout;
           if (!resize_size.empty()) {
             // a window of every image resized to resize_size = (oh, ow): window = B x (y0, x0, h, w, mirrored)
             if (resize_size.size() != 2 || B < 0 || window.size() != size_t(B) * 5 || !crop_size.empty())
@@ -330,14 +336,7 @@ PYBIND11_MODULE(_hip, m) {
             d.y0[b] = int16_t(regions[size_t(b) * 4]), d.y1[b] = int16_t(regions[size_t(b) * 4 + 1]);
             d.x0[b] = int16_t(regions[size_t(b) * 4 + 2]), d.x1[b] = int16_t(regions[size_t(b) * 4 + 3]);
           }
-          p.max_grid = max_grid;
-          p.dst = ptr<void>(dst);
-          p.lut = ptr<const float>(lut);
-          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
-          fill_cmap(p.cmap, cmap);
-          p.flip_all = flip_all;
-          p.out_dtype = out_dtype;
-          p.layout = layout;
+          fill_scalars(p, dst, lut, B, H, W, Cin, Cout, cmap, flip_all, out_dtype, layout, max_grid);
           check(decode_delta(p, d, stream_of(stream)), "decode_delta");
         },
         py::arg("srcs"), py::arg("mirrors"), py::arg("regions"), py::arg("dst"), py::arg("lut"), py::arg("B"),
@@ -371,14 +370,7 @@ PYBIND11_MODULE(_hip, m) {
               d.mask[b][k] = uint16_t(mk[k]);
             }
           }
-          p.max_grid = max_grid;
-          p.dst = ptr<void>(dst);
-          p.lut = ptr<const float>(lut);
-          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
-          fill_cmap(p.cmap, cmap);
-          p.flip_all = flip_all;
-          p.out_dtype = out_dtype;
-          p.layout = layout;
+          fill_scalars(p, dst, lut, B, H, W, Cin, Cout, cmap, flip_all, out_dtype, layout, max_grid);
           check(decode_delta_blocks(p, d, stream_of(stream)), "decode_delta_blocks");
         },
         py::arg("srcs"), py::arg("mirrors"), py::arg("band_rows"), py::arg("masks"), py::arg("dst"), py::arg("lut"),
@@ -404,15 +396,8 @@ PYBIND11_MODULE(_hip, m) {
           const size_t elem = out_dtype == OUT_F32 ? 4 : (out_dtype == OUT_U8 ? 1 : 2);
           t.out_img_bytes = int64_t(size_t(H) * size_t(W) * size_t(Cout) * elem);
           t.payload_off = int64_t(tiledelta::payload_offset(H, W));
-          p.max_grid = max_grid;
-          p.dst = ptr<void>(dst);
-          p.lut = ptr<const float>(lut);
+          fill_scalars(p, dst, lut, B, H, W, Cin, Cout, cmap, flip_all, out_dtype, layout, max_grid);
           p.flip = ptr<const uint8_t>(flip);
-          p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
-          fill_cmap(p.cmap, cmap);
-          p.flip_all = flip_all;
-          p.out_dtype = out_dtype;
-          p.layout = layout;
           check(decode_tiles(p, t, stream_of(stream)), "decode_tiles");
         },
         py::arg("srcs"), py::arg("fills"), py::arg("tile_start"), py::arg("dst"), py::arg("lut"), py::arg("flip"),

@@ -15,8 +15,8 @@
 //
 // This header keeps, per mapped ring, which generation the mirror holds for
 // every slot, and decides per frame which region or blocks the kernel has to
-// read from the host (kernels.h: decode_delta, decode_delta_blocks).  It never
-// looks at pixels.
+// read from the host (kernels.h: decode_delta, decode_delta_blocks -- one
+// kernel body with two inside tests).  It never looks at pixels.
 #pragma once
 
 #include <cstddef>
@@ -144,16 +144,8 @@ class Ring {
   // holds `gen` (the caller queues the kernel that makes it so).
   // *from_delta: the report was used.
   Region decide(uint32_t slot, uint32_t gen, const Delta* d, int H, int W, bool* from_delta = nullptr) {
-    Region r;
-    const bool use = d && slot < gen_.size() && holds(slot, d->base_gen) && delta_valid(*d, H, W);
-    if (use) {
-      r = widen(d->rect, W);
-    } else {
-      r.y0 = 0, r.y1 = H - 1, r.x0 = 0, r.x1 = W - 1;
-    }
-    if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
-    if (from_delta) *from_delta = use;
-    return r;
+    if (accept(slot, gen, d, H, W, from_delta)) return widen(d->rect, W);
+    return Region{0, H - 1, 0, W - 1};
   }
   // decide() in blocks (decode_delta_blocks): the mask to read from the host,
   // always on the grid blocks::band_rows_for(H), one grid per launch -- the
@@ -164,7 +156,7 @@ class Ring {
   BlockMask decide_blocks(uint32_t slot, uint32_t gen, const Delta* d, const BlockMask* reported, int H, int W,
                           bool* from_delta = nullptr, bool* from_blocks = nullptr) {
     BlockMask m;
-    const bool use = d && slot < gen_.size() && holds(slot, d->base_gen) && delta_valid(*d, H, W);
+    const bool use = accept(slot, gen, d, H, W, from_delta);
     const bool fine = use && reported && reported->band_rows == blocks::band_rows_for(H) && blocks::width_ok(W);
     if (fine) {
       m = *reported;
@@ -174,13 +166,21 @@ class Ring {
       m.band_rows = blocks::band_rows_for(H);
       for (int k = 0, nb = blocks::bands(H, m.band_rows); k < nb; ++k) m.w[k] = blocks::all_columns(W);
     }
-    if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
-    if (from_delta) *from_delta = use;
     if (from_blocks) *from_blocks = fine;
     return m;
   }
 
  private:
+  // The step both decisions share: is the report usable (the mirror holds the
+  // generation it is relative to, and its rectangle lies in the frame)?  Then
+  // the mirror holds `gen` for the slot.
+  bool accept(uint32_t slot, uint32_t gen, const Delta* d, int H, int W, bool* from_delta) {
+    const bool use = d && holds(slot, d->base_gen) && delta_valid(*d, H, W);
+    if (slot < gen_.size()) gen_[slot] = gen, held_[slot] = 1;
+    if (from_delta) *from_delta = use;
+    return use;
+  }
+
   std::vector<uint32_t> gen_;
   std::vector<uint8_t> held_;
 };

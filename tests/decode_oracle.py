@@ -18,12 +18,14 @@ everything around it, on the CPU and with no code of the kernels' launchers:
 ``mutate=`` alters exactly one rule (:data:`MUTATIONS`): the tests use it to prove
 that their inputs would expose that slip.
 """
+import ctypes
 import dataclasses
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
+from blendtorch import ops
 from blendtorch.ops import DecodeConfig, reference_color4x4, reference_decode
 
 TILE = 16
@@ -383,3 +385,69 @@ def expected(l: Launch, mutate=None):
 def regions(l: Launch):
     """``[(buffer, offset, nbytes)]`` of the images, for tests that compare them as numbers."""
     return [(k, off, l.img_bytes) for k, off in l.dst]
+
+
+class MirrorLaunch:
+    """The buffers of one slot-mirror launch (``decode_delta``, ``decode_delta_blocks``) and what it must leave.
+
+    ``inside[b]`` (bool H x W x Cin, b >= 1) says which bytes of image b the kernel has to take from the
+    host; image 0 has no mirror and is read whole.  The host frames (pinned, device-mapped) hold the true
+    bytes inside and POISON outside, the mirrors the true bytes outside and poison inside; outputs and
+    the space around the mirrors are guard-filled.  ``launch(self, **kw)`` hands the buffers to a binding.
+    """
+
+    def __init__(self, dev, store, cfg, inside, launch, flip_bits, label=''):
+        self.dev, self.store, self.cfg, self.flip_bits, self.label, self._launch = dev, store, cfg, flip_bits, label, launch
+        self.B, self.H, self.W, self.Cin = store.shape
+        self.fb = self.H * self.W * self.Cin
+        self.img_bytes = self.H * self.W * cfg.cout * ELEM[cfg.dtype]
+        self.bufs, self.dst = scattered_dst([(b % 2, b // 2) for b in range(self.B)], self.img_bytes, nbufs=2)
+        self.ins = [np.ones_like(store[0], bool)] + list(inside)
+        host = np.stack([np.where(i, t, t ^ 0xFF).reshape(-1) for i, t in zip(self.ins, store)])
+        mir = np.full(GUARD + (self.B - 1) * (self.fb + GUARD), SENTINEL, np.uint8)
+        self.mir_off = [None] + [GUARD + (b - 1) * (self.fb + GUARD) for b in range(1, self.B)]
+        for b in range(1, self.B):
+            mir[self.mir_off[b]:self.mir_off[b] + self.fb] = np.where(self.ins[b], store[b] ^ 0xFF, store[b]).reshape(-1)
+        self.host0, self.mir0 = host, mir.copy()
+        self.host, self.host_dev = ops.hip_ext().host_mapped_alloc(host.size)
+        ctypes.memmove(self.host, host.ctypes.data, host.size)
+        self.mir = torch.from_numpy(mir).to(dev)
+        self.outs = [torch.full((n,), SENTINEL, dtype=torch.uint8, device=dev) for n in self.bufs]
+
+    def close(self):
+        ops.hip_ext().host_mapped_free(self.host)
+
+    def launch(self, **kw):
+        self._launch(self, **kw)
+        torch.cuda.synchronize()
+
+    def untouched(self):
+        """Nothing was launched: outputs and mirrors are what they were."""
+        assert all(bool((o == SENTINEL).all()) for o in self.outs)
+        assert np.array_equal(self.mir.cpu().numpy(), self.mir0)
+
+    def reference(self):
+        """``ops.reference_decode`` of the true frames, as bytes per image."""
+        flags = [(self.flip_bits >> b) & 1 for b in range(self.B)]
+        ref = reference_decode(torch.from_numpy(self.store), self.cfg, flip=flags)
+        return ref.contiguous().view(torch.uint8).reshape(self.B, -1).numpy()
+
+    def check(self, what, ref=None):
+        """Every output buffer, guards included, equals the reference; every mirror its true frame."""
+        ref = self.reference() if ref is None else ref
+        exp = [np.full(n, SENTINEL, np.uint8) for n in self.bufs]
+        for b, (k, off) in enumerate(self.dst):
+            exp[k][off:off + self.img_bytes] = ref[b]
+        for k, (o, e) in enumerate(zip(self.outs, exp)):
+            g = o.cpu().numpy()
+            if not np.array_equal(g, e):
+                bad = np.flatnonzero(g != e)
+                where = [b for b, (kk, off) in enumerate(self.dst) if kk == k and off <= bad[0] < off + self.img_bytes]
+                raise AssertionError(f'{what}: W {self.W} Cin {self.Cin} {self.cfg.channels} {self.label}: '
+                                     f'buffer {k}: {len(bad)} bytes differ, first at {bad[0]} '
+                                     f'({"image %d" % where[0] if where else "GUARD"})')
+        m = self.mir.cpu().numpy()
+        want = np.full(m.size, SENTINEL, np.uint8)
+        for b in range(1, self.B):
+            want[self.mir_off[b]:self.mir_off[b] + self.fb] = self.store[b].reshape(-1)
+        assert np.array_equal(m, want), f'{what}: the mirrors do not equal the true frames (or a guard was written)'

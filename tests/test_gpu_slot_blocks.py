@@ -17,13 +17,12 @@ Loader: stamped 128x64 cubesim frames, random poses, from two 4-slot rings,
 batch 4, 12 batches, and from two 24-slot rings in batches of 40 (more than one
 block launch holds); the oracle is the same frames through the CPU path.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from decode_oracle import ELEM, GUARD, SENTINEL, frames, scattered_dst
+from decode_oracle import MirrorLaunch, frames
+from test_gpu_slot_delta import _Delta
 from blendtorch import btt, ops
 from blendtorch.btt.gpu import DeviceLoader
 from blendtorch.ops import DecodeConfig
@@ -67,97 +66,47 @@ def _masks(band_rows):
     }
 
 
-def _inside(mask, band_rows, Cin):
+def _inside(mask, band_rows, Cin, H=H, W=W):
     m = np.zeros((H, W, Cin), bool)
     for k, word in enumerate(mask):
-        for c in range(NCOL):
+        for c in range(W // 64):
             if (word >> c) & 1:
                 m[k * band_rows:(k + 1) * band_rows, 64 * c:64 * c + 64] = True
     return m
 
 
-class _Blocks:
+def _launch(d, B=None, band_rows=None, masks=None, W_=None):
+    masks = d.masks if masks is None else masks
+    B = d.B if B is None else B
+    last = d.B - 1
+    ops.hip_ext().decode_delta_blocks(
+        [d.host_dev + min(b, last) * d.fb for b in range(B)],
+        [0 if b == 0 else d.mir.data_ptr() + d.mir_off[min(b, last)] for b in range(B)],
+        d.band_rows if band_rows is None else band_rows,
+        [masks[min(b, last)] for b in range(B)], 0, ops.device_lut(d.cfg, d.dev).data_ptr(),
+        B, d.H, d.W if W_ is None else W_, d.Cin, d.cfg.cout, list(d.cfg.cmap), 0,
+        ops.OUT_DTYPES[d.cfg.dtype], ops.LAYOUTS[d.cfg.layout], ops._stream(d.dev),
+        dsts=[d.outs[d.dst[min(b, last)][0]].data_ptr() + d.dst[min(b, last)][1] for b in range(B)],
+        flip_bits=[d.flip_bits])
+
+
+def _Blocks(dev, store, cfg, band_rows, masks, flip_bits):
     """One decode_delta_blocks launch; image 0 has no mirror, images 1.. use ``masks``."""
-
-    def __init__(self, dev, store, cfg, band_rows, masks, flip_bits):
-        self.dev, self.store, self.cfg, self.flip_bits, self.band_rows = dev, store, cfg, flip_bits, band_rows
-        self.B, _, _, self.Cin = store.shape
-        self.masks = [[0] * len(masks[0])] + [list(m) for m in masks]
-        self.fb = H * W * self.Cin
-        self.img_bytes = H * W * cfg.cout * ELEM[cfg.dtype]
-        self.bufs, self.dst = scattered_dst([(b % 2, b // 2) for b in range(self.B)], self.img_bytes, nbufs=2)
-        ext = ops.hip_ext()
-        # host frames: true inside the set blocks, poison outside (image 0: all true)
-        host = np.empty((self.B, self.fb), np.uint8)
-        mir = np.full(GUARD + (self.B - 1) * (self.fb + GUARD), SENTINEL, np.uint8)
-        self.mir_off = [None] + [GUARD + (b - 1) * (self.fb + GUARD) for b in range(1, self.B)]
-        self.ins = []
-        for b in range(self.B):
-            true = store[b]
-            ins = np.ones_like(true, bool) if b == 0 else _inside(self.masks[b], band_rows, self.Cin)
-            self.ins.append(ins)
-            host[b] = np.where(ins, true, true ^ 0xFF).reshape(-1)
-            if b:
-                mir[self.mir_off[b]:self.mir_off[b] + self.fb] = np.where(ins, true ^ 0xFF, true).reshape(-1)
-        self.host, self.host_dev = ext.host_mapped_alloc(host.size)
-        ctypes.memmove(self.host, host.ctypes.data, host.size)
-        self.mir = torch.from_numpy(mir).to(dev)
-        self.outs = [torch.full((n,), SENTINEL, dtype=torch.uint8, device=dev) for n in self.bufs]
-
-    def close(self):
-        ops.hip_ext().host_mapped_free(self.host)
-
-    def launch(self, B=None, band_rows=None, masks=None, W_=None):
-        masks = self.masks if masks is None else masks
-        B = self.B if B is None else B
-        last = self.B - 1
-        ops.hip_ext().decode_delta_blocks(
-            [self.host_dev + min(b, last) * self.fb for b in range(B)],
-            [0 if b == 0 else self.mir.data_ptr() + self.mir_off[min(b, last)] for b in range(B)],
-            self.band_rows if band_rows is None else band_rows,
-            [masks[min(b, last)] for b in range(B)], 0, ops.device_lut(self.cfg, self.dev).data_ptr(),
-            B, H, W if W_ is None else W_, self.Cin, self.cfg.cout, list(self.cfg.cmap), 0,
-            ops.OUT_DTYPES[self.cfg.dtype], ops.LAYOUTS[self.cfg.layout], ops._stream(self.dev),
-            dsts=[self.outs[self.dst[min(b, last)][0]].data_ptr() + self.dst[min(b, last)][1] for b in range(B)],
-            flip_bits=[self.flip_bits])
-        torch.cuda.synchronize()
-
-    def untouched(self):
-        """Nothing was launched: outputs and mirrors are what they were."""
-        assert all(bool((o == SENTINEL).all()) for o in self.outs)
-        m = self.mir.cpu().numpy()
-        for b in range(1, self.B):
-            assert np.array_equal(m[self.mir_off[b]:self.mir_off[b] + self.fb],
-                                  np.where(self.ins[b], self.store[b] ^ 0xFF, self.store[b]).reshape(-1))
-
-    def check(self, what, ref):
-        exp = [np.full(n, SENTINEL, np.uint8) for n in self.bufs]
-        for b, (k, off) in enumerate(self.dst):
-            exp[k][off:off + self.img_bytes] = ref[b]
-        for k, (o, e) in enumerate(zip(self.outs, exp)):
-            g = o.cpu().numpy()
-            if not np.array_equal(g, e):
-                bad = np.flatnonzero(g != e)
-                where = [b for b, (kk, off) in enumerate(self.dst) if kk == k and off <= bad[0] < off + self.img_bytes]
-                raise AssertionError(f'{what}: Cin {self.Cin} {self.cfg.channels} band_rows {self.band_rows} masks '
-                                     f'{self.masks}: buffer {k}: {len(bad)} bytes differ, first at {bad[0]} '
-                                     f'({"image %d" % where[0] if where else "GUARD"})')
-        m = self.mir.cpu().numpy()
-        want = np.full(m.size, SENTINEL, np.uint8)
-        for b in range(1, self.B):
-            want[self.mir_off[b]:self.mir_off[b] + self.fb] = self.store[b].reshape(-1)
-        assert np.array_equal(m, want), f'{what}: the mirrors do not equal the true frames (or a guard was written)'
+    _, h, w, Cin = store.shape
+    d = MirrorLaunch(dev, store, cfg, [_inside(m, band_rows, Cin, h, w) for m in masks], _launch, flip_bits)
+    d.band_rows = band_rows
+    d.masks = [[0] * len(masks[0])] + [list(m) for m in masks]
+    d.label = f'band_rows {band_rows} masks {d.masks}'
+    return d
 
 
 _ref_cache = {}
 
 
-def _reference(store, cfg, flip_bits, key):
-    """ops.reference_decode of the true frames, as bytes per image; computed once per (frames, config)."""
+def _reference(d, key):
+    """The launch's reference bytes per image; computed once per (frames, config)."""
     if key not in _ref_cache:
-        flags = [(flip_bits >> b) & 1 for b in range(store.shape[0])]
-        ref = ops.reference_decode(torch.from_numpy(store), cfg, flip=flags)
-        _ref_cache[key] = ref.contiguous().view(torch.uint8).reshape(store.shape[0], -1).numpy()
+        _ref_cache[key] = d.reference()
     return _ref_cache[key]
 
 
@@ -174,7 +123,7 @@ def test_set_blocks_from_host_rest_from_mirror(dev, dtype, layout, band_rows):
         d = _Blocks(dev, store, cfg, band_rows, [masks[n] for n in names], flip_bits)
         try:
             d.launch()
-            d.check('/'.join(names), _reference(store, cfg, flip_bits, (Cin, ch, dtype, layout)))
+            d.check('/'.join(names), _reference(d, (Cin, ch, dtype, layout)))
         finally:
             d.close()
 
@@ -208,9 +157,41 @@ def test_rejections_launch_nothing(dev):
             d.launch(masks=[d.masks[0], [0] * 5 + [1], d.masks[2]])                # band 5 of 5
         d.untouched()
         d.launch()
-        d.check('after the rejections', _reference(store, cfg, 0b010, 'rejections'))
+        d.check('after the rejections', _reference(d, 'rejections'))
     finally:
         d.close()
+
+
+def _rect_blocks(region, nb, band_rows):
+    """slot_mirror.h rect_blocks on a grid of ``band_rows``: the blocks a (widened) region touches."""
+    y0, y1, x0, x1 = region
+    bits = (2 << (x1 // 64)) - (1 << (x0 // 64)) if y1 >= y0 else 0
+    return [bits if y0 // band_rows <= k <= y1 // band_rows else 0 for k in range(nb)]
+
+
+@pytest.mark.parametrize('dtype,layout', [('float32', 'nchw'), ('uint8', 'nhwc')])
+@pytest.mark.parametrize('Cin,ch', [(3, 'bgr'), (4, 'rgb')])
+def test_a_rectangle_read_and_its_block_read_agree(dev, Cin, ch, dtype, layout):
+    """The loader hands a rectangle-only producer's frames to the block read (rect_blocks): both reads of
+    one rectangle on band and 64-column boundaries, over identical poisoned inputs, leave identical
+    output and mirror bytes, equal to the reference.  Image 0 has no mirror, image 1 is flipped."""
+    RH, RW, band_rows, flip_bits = 24, 128, 8, 0b010
+    store = frames(3, RH, RW, Cin, seed=1200 + Cin)
+    cfg = _vcfg(ch, dtype, layout)
+    for regions in ([(8, 15, 64, 127), (0, -1, 0, -1)], [(0, RH - 1, 0, RW - 1), (8, 15, 64, 127)]):
+        r = _Delta(dev, store, cfg, regions, flip_bits)
+        b = _Blocks(dev, store, cfg, band_rows, [_rect_blocks(g, RH // band_rows, band_rows) for g in regions], flip_bits)
+        try:
+            assert np.array_equal(r.mir0, b.mir0) and np.array_equal(r.host0, b.host0)
+            r.launch()
+            b.launch()
+            ref = r.reference()
+            r.check('rectangle read', ref)
+            b.check('block read', ref)
+            assert all(torch.equal(x, y) for x, y in zip(r.outs, b.outs)) and torch.equal(r.mir, b.mir)
+        finally:
+            r.close()
+            b.close()
 
 
 # ---- loader -------------------------------------------------------------------------------------------------------

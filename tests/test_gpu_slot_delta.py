@@ -12,7 +12,6 @@ every mirror equals its true frame and the guards around the mirrors hold.
 
 Loader: stamped 64x48 cubesim frames from 4-slot rings, batch 4, 10 batches.
 """
-import ctypes
 import os
 import struct
 
@@ -20,7 +19,7 @@ import numpy as np
 import pytest
 import torch
 
-from decode_oracle import ELEM, GUARD, SENTINEL, frames, scattered_dst
+from decode_oracle import MirrorLaunch, frames
 from blendtorch import btt, ops
 from blendtorch.btt.gpu import DeviceLoader
 from blendtorch.ops import DecodeConfig
@@ -58,84 +57,32 @@ def _regions(W):
     }
 
 
-def _inside(region, W, Cin):
+def _inside(region, shape):
     y0, y1, x0, x1 = region
-    m = np.zeros((H, W, Cin), bool)
+    m = np.zeros(shape, bool)
     if y1 >= y0:
         m[y0:y1 + 1, x0:x1 + 1] = True
     return m
 
 
-class _Delta:
+def _launch(d, B=None, regions=None, cmap=None, W=None):
+    regions = d.regions if regions is None else regions
+    B = d.B if B is None else B
+    ops.hip_ext().decode_delta(
+        [d.host_dev + b * d.fb for b in range(min(B, d.B))],
+        [0 if b == 0 or b >= d.B else d.mir.data_ptr() + d.mir_off[b] for b in range(B)],
+        [v for b in range(B) for v in regions[min(b, d.B - 1)]], 0, ops.device_lut(d.cfg, d.dev).data_ptr(),
+        B, d.H, d.W if W is None else W, d.Cin, d.cfg.cout, list(d.cfg.cmap) if cmap is None else cmap, 0,
+        ops.OUT_DTYPES[d.cfg.dtype], ops.LAYOUTS[d.cfg.layout], ops._stream(d.dev),
+        dsts=[d.outs[k].data_ptr() + off for k, off in d.dst][:B], flip_bits=[d.flip_bits])
+
+
+def _Delta(dev, store, cfg, regions, flip_bits=0b010):
     """One decode_delta launch; image 0 has no mirror, images 1.. use ``regions``."""
-
-    def __init__(self, dev, store, cfg, regions, flip_bits=0b010):
-        self.dev, self.store, self.cfg, self.flip_bits = dev, store, cfg, flip_bits
-        self.B, _, self.W, self.Cin = store.shape
-        self.regions = [(0, -1, 0, -1)] + list(regions)
-        self.fb = H * self.W * self.Cin
-        self.img_bytes = H * self.W * cfg.cout * ELEM[cfg.dtype]
-        self.bufs, self.dst = scattered_dst([(b % 2, b // 2) for b in range(self.B)], self.img_bytes, nbufs=2)
-        ext = ops.hip_ext()
-        # host frames: true inside the region, poison outside (image 0: all true)
-        host = np.empty((self.B, self.fb), np.uint8)
-        mir = np.full(GUARD + (self.B - 1) * (self.fb + GUARD), SENTINEL, np.uint8)
-        self.mir_off = [None] + [GUARD + (b - 1) * (self.fb + GUARD) for b in range(1, self.B)]
-        for b in range(self.B):
-            true = store[b]
-            ins = np.ones_like(true, bool) if b == 0 else _inside(self.regions[b], self.W, self.Cin)
-            host[b] = np.where(ins, true, true ^ 0xFF).reshape(-1)
-            if b:
-                mir[self.mir_off[b]:self.mir_off[b] + self.fb] = np.where(ins, true ^ 0xFF, true).reshape(-1)
-        self.host, self.host_dev = ext.host_mapped_alloc(host.size)
-        ctypes.memmove(self.host, host.ctypes.data, host.size)
-        self.mir = torch.from_numpy(mir).to(dev)
-        self.outs = [torch.full((n,), SENTINEL, dtype=torch.uint8, device=dev) for n in self.bufs]
-
-    def close(self):
-        ops.hip_ext().host_mapped_free(self.host)
-
-    def launch(self, B=None, regions=None, cmap=None, W=None):
-        regions = self.regions if regions is None else regions
-        B = self.B if B is None else B
-        ops.hip_ext().decode_delta(
-            [self.host_dev + b * self.fb for b in range(min(B, self.B))],
-            [0 if b == 0 or b >= self.B else self.mir.data_ptr() + self.mir_off[b] for b in range(B)],
-            [v for b in range(B) for v in regions[min(b, self.B - 1)]], 0, ops.device_lut(self.cfg, self.dev).data_ptr(),
-            B, H, self.W if W is None else W, self.Cin, self.cfg.cout, list(self.cfg.cmap) if cmap is None else cmap, 0,
-            ops.OUT_DTYPES[self.cfg.dtype], ops.LAYOUTS[self.cfg.layout], ops._stream(self.dev),
-            dsts=[self.outs[k].data_ptr() + off for k, off in self.dst][:B], flip_bits=[self.flip_bits])
-        torch.cuda.synchronize()
-
-    def untouched(self):
-        """Nothing was launched: outputs and mirrors are what they were."""
-        assert all(bool((o == SENTINEL).all()) for o in self.outs)
-        m = self.mir.cpu().numpy()
-        for b in range(1, self.B):
-            ins = _inside(self.regions[b], self.W, self.Cin)
-            assert np.array_equal(m[self.mir_off[b]:self.mir_off[b] + self.fb],
-                                  np.where(ins, self.store[b] ^ 0xFF, self.store[b]).reshape(-1))
-
-    def check(self, what):
-        flags = [(self.flip_bits >> b) & 1 for b in range(self.B)]
-        ref = ops.reference_decode(torch.from_numpy(self.store), self.cfg, flip=flags)
-        ref = ref.contiguous().view(torch.uint8).reshape(self.B, -1).numpy()
-        exp = [np.full(n, SENTINEL, np.uint8) for n in self.bufs]
-        for b, (k, off) in enumerate(self.dst):
-            exp[k][off:off + self.img_bytes] = ref[b]
-        for k, (o, e) in enumerate(zip(self.outs, exp)):
-            g = o.cpu().numpy()
-            if not np.array_equal(g, e):
-                bad = np.flatnonzero(g != e)
-                where = [b for b, (kk, off) in enumerate(self.dst) if kk == k and off <= bad[0] < off + self.img_bytes]
-                raise AssertionError(f'{what}: W {self.W} Cin {self.Cin} {self.cfg.channels} regions {self.regions}: '
-                                     f'buffer {k}: {len(bad)} bytes differ, first at {bad[0]} '
-                                     f'({"image %d" % where[0] if where else "GUARD"})')
-        m = self.mir.cpu().numpy()
-        want = np.full(m.size, SENTINEL, np.uint8)
-        for b in range(1, self.B):
-            want[self.mir_off[b]:self.mir_off[b] + self.fb] = self.store[b].reshape(-1)
-        assert np.array_equal(m, want), f'{what}: the mirrors do not equal the true frames (or a guard was written)'
+    d = MirrorLaunch(dev, store, cfg, [_inside(r, store.shape[1:]) for r in regions], _launch, flip_bits)
+    d.regions = [(0, -1, 0, -1)] + list(regions)
+    d.label = f'regions {d.regions}'
+    return d
 
 
 @pytest.mark.parametrize('layout', LAYOUTS)
