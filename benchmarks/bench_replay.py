@@ -4,6 +4,7 @@ batches gathered + decoded by one fused kernel per batch.
 
     python benchmarks/bench_replay.py [--frames 4096] [--batch 8] [--steps 2000] [--fill producers|synthetic]
                                       [--crop H W] [--pad P] [--mirror p]
+                                      [--stack K [--stride S] [--nstep N [--gamma G]]]
 
 ``--fill producers`` streams the frames from headless Cube producers through
 a raw-u8 DeviceLoader (the record-once, train-many-epochs workflow);
@@ -11,6 +12,8 @@ a raw-u8 DeviceLoader (the record-once, train-many-epochs workflow);
 ``--crop H W`` samples through random windows (``--mirror p``: mirrored with
 probability p; ``--pad P``: replicate padding, ``--crop 480 640 --pad 4`` is
 the random shift of DrQ / RAD) inside the same launch.
+``--stack K`` times frame-stacked transitions, ``--stack K --nstep N`` the
+n-step sample against the 1-step one and against the path composed on top of it.
 Prints one JSON line (images/s of decoded fp32 CHW batches); ``effective_tbps``
 counts the bytes read (the window's) plus the bytes written.
 """
@@ -102,6 +105,75 @@ def bench_stack(a, rb, cfg, fill_s):
                                                          'mirror': crop.mirror}}), flush=True)
 
 
+def bench_nstep(a, rb, cfg, fill_s):
+    """--stack K --nstep N: the fused n-step sample, the fused 1-step sample and the n-step batch composed on
+    top of the 1-step sample, timed in this process, two rounds each."""
+    import torch
+    dev, B, K, S, N = rb.device, a.batch, a.stack, a.stride, a.nstep
+    cap = rb.capacity
+    kw = dict(stack=K, stride=S, next_keys=('reward',))
+    nkw = dict(nstep=N, gamma=a.gamma, done_key='done')
+    if a.graph:
+        fused_n, fused_1 = rb.graphed_transition_sampler(B, cfg, **kw, **nkw), rb.graphed_transition_sampler(B, cfg, **kw)
+    else:
+        fused_n, fused_1 = (lambda: rb.sample_transitions(B, cfg, **kw, **nkw)), (lambda: rb.sample_transitions(B, cfg, **kw))
+    reward, done, first = rb.meta['reward'], rb.meta['done'], rb.meta['first']
+
+    # what a user writes on the 1-step API: the fused 1-step sample, N - 1 rounds of metadata gathers with the
+    # flag walk in torch, and one more transition gather at c_{m-1} for the stack at c_m.  It runs eagerly
+    # also with --graph (the second gather's anchors come out of the walk)
+    def composed():
+        b = rb.sample_transitions(B, cfg, **kw)
+        c0, alive = b['index'], b['valid'].clone()
+        age0 = (rb._next - 1 - c0) % cap
+        steps = alive.to(torch.int32)
+        ret = torch.where(alive, b['reward'], torch.zeros_like(b['reward']))
+        g = torch.full_like(ret, a.gamma)
+        for j in range(1, N):
+            alive = (alive & (done.index_select(0, (c0 + (j - 1) * S) % cap) == 0) & (age0 - j * S >= S)
+                     & (first.index_select(0, (c0 + (j + 1) * S) % cap) == 0))
+            ret = torch.where(alive, ret + g * reward.index_select(0, (c0 + j * S) % cap), ret)
+            g = torch.where(alive, g * a.gamma, g)
+            steps = steps + alive.to(torch.int32)
+        last = (c0 + (steps.to(torch.int64) - 1).clamp(min=0) * S) % cap
+        term = b['valid'] & (done.index_select(0, last) != 0)
+        nxt = rb.gather_transitions(last, cfg, **kw)
+        b.update(next_obs=nxt['next_obs'], next_index=nxt['next_index'], next_reward=nxt['next_reward'],
+                 nstep_return=ret, nstep_discount=torch.where(term | ~b['valid'], torch.zeros_like(g), g),
+                 nstep_steps=steps)
+        return b
+
+    rows = {f'fused {N}-step': fused_n, 'fused 1-step': fused_1, f'composed {N}-step': composed}
+    times = {k: [] for k in rows}
+    for _ in range(2):
+        for name, fn in rows.items():
+            for _ in range(a.warmup):
+                fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                b = fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / a.steps * 1e6)
+            del b
+    us = {k: min(v) for k, v in times.items()}
+    for name, v in times.items():
+        print(f'{name:20s} {us[name]:10.2f} us/batch   (rounds: {", ".join("%.2f" % t for t in v)})', flush=True)
+    un, u1, uc = (us[k] for k in rows)
+    print(f'n-step / 1-step      {un / u1:10.3f}', flush=True)
+    print(f'n-step / composed    {un / uc:10.3f}', flush=True)
+    H, W, C = rb.frame_shape
+    print(json.dumps({'metric': 'replay n-step transitions us/batch (HBM store -> obs, next_obs, n-step return)',
+                      'value': round(un, 2), 'unit': 'us/batch', 'batch': B, 'stack': K, 'stride': S, 'nstep': N,
+                      'gamma': a.gamma, 'graph': a.graph, 'dtype': a.dtype, 'frame': [H, W, C], 'frames': a.frames,
+                      'us_per_batch': {k: round(v, 2) for k, v in us.items()},
+                      'rounds_us': {k: [round(t, 2) for t in v] for k, v in times.items()},
+                      'nstep_over_1step': round(un / u1, 3), 'nstep_over_composed': round(un / uc, 3),
+                      'fill_s': round(fill_s, 2),
+                      'crop': None if cfg.crop is None else {'size': list(cfg.crop.size), 'pad': cfg.crop.pad,
+                                                             'mirror': cfg.crop.mirror}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=4096)
@@ -122,6 +194,10 @@ def main():
                     help='frame-stacked transitions: time the fused sample_transitions, the composed path '
                          '(2K gathers + cat) and the equal-bytes plain sample (synthetic fill)')
     ap.add_argument('--stride', type=int, default=1, metavar='S', help='frames per environment step (--stack)')
+    ap.add_argument('--nstep', type=int, default=0, metavar='N',
+                    help='with --stack: time the fused N-step sample, the fused 1-step sample and the N-step '
+                         'batch composed on top of the 1-step sample')
+    ap.add_argument('--gamma', type=float, default=0.99, help='discount of --nstep')
     ap.add_argument('--frame', type=int, nargs=3, metavar=('H', 'W', 'C'), default=(480, 640, 4),
                     help='frame shape of the synthetic store')
     a = ap.parse_args()
@@ -131,6 +207,8 @@ def main():
         ap.error('--crop needs the fused sampler')
     if a.stack and (a.fill != 'synthetic' or a.sampler != 'fused'):
         ap.error('--stack needs the synthetic fill and the fused sampler')
+    if a.nstep and not a.stack:
+        ap.error('--nstep needs --stack')
     if a.fill != 'synthetic' and tuple(a.frame) != (480, 640, 4):
         ap.error('--frame needs the synthetic fill')
 
@@ -149,6 +227,8 @@ def main():
             meta = {'frameid': ids}
             if a.stack:   # an episode starts every 100 steps of every environment
                 meta.update(first=((ids // a.stride) % 100 == 0).to(torch.uint8), reward=ids.to(torch.float32))
+            if a.nstep:   # every other episode terminates (its last step), the others are truncated
+                meta.update(done=((ids // a.stride) % 200 == 98).to(torch.uint8))
             rb.extend(torch.randint(0, 256, (n, fh, fw, fc), dtype=torch.uint8, device=dev, generator=g), **meta)
     else:
         from blendtorch.btt.gpu import DeviceLoader
@@ -161,6 +241,8 @@ def main():
     fill_s = time.perf_counter() - t0
     crop = None if a.crop is None else ops.Crop(tuple(a.crop), mirror=a.mirror, pad=a.pad)
     cfg = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, dtype=a.dtype, crop=crop)
+    if a.nstep:
+        return bench_nstep(a, rb, cfg, fill_s)
     if a.stack:
         return bench_stack(a, rb, cfg, fill_s)
 

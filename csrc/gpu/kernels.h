@@ -324,6 +324,37 @@ hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, cons
 // capacity > 2^31, by value size <= stride, size > capacity or head outside
 // [0, capacity), no `first`, a layout other than NCHW, and everything
 // replay_sample_crop refuses.
+//
+// MULTI-STEP RETURNS (nstep = n in [1, 16]; 0: off -- everything above, the
+// table and the code path included, is then exactly as without the fields).
+// `reward` (fp32 [capacity]): reward[s] is the reward of the step taken from
+// slot s; `done` (nullable, u8 [capacity]): done[s] != 0 iff the step taken
+// from s terminated the episode; gamma an fp32 in [0, 1].  For an image with
+// anchor c_0 and c_j = (c_0 + j S) mod capacity:
+//   * anchor validity and the candidate draw are the 1-step ones (the step
+//     c_0 -> c_1 exists and first[c_1] == 0): index_out does not depend on n.
+//   * number of steps m: 0 for an invalid image; else m starts at 1 and grows
+//     while m < n, and (no done column or done[c_{m-1}] == 0), and c_{m+1} is
+//     stored (age(c_0) - m S >= S), and first[c_{m+1}] == 0.
+//     terminated = done column present and done[c_{m-1}] != 0 (valid images).
+//   * return_out (fp32 [B]): g = 1; R = 0; for j < m: R = R + g * reward[c_j];
+//     g = g * gamma -- every multiply and add a separate fp32
+//     round-to-nearest operation, never contracted into an FMA: a float32
+//     loop on the host gives the same bits.  discount_out (fp32 [B]): g after the loop, 0 if
+//     terminated or invalid.  steps_out (int32 [B]): m.
+//   * next_index_out = c_m (the anchor if invalid); next_* metadata rows of c_m.
+//   * frame table e[b][0 .. k - 1 + n]: e[0 .. k - 1] as above, and
+//     e[k - 1 + j] = c_{min(j, m)} for j <= n.  next_obs is the k frames
+//     ending at c_m, oldest first: frame f is e[max(m, 1) + f] (c_1 .. c_m
+//     cross no first frame, so it is the obs walk extended forward; an
+//     invalid image keeps e[1 .. k] with e[k] = anchor).  The first / done
+//     flags the walk needs are read at slots reduced mod capacity: no byte
+//     outside the columns is read whatever they hold.
+//   * windows, the counter advance and the device (head, size) state: unchanged.
+// Refused as well (hipErrorInvalidValue, nothing launched) when nstep != 0:
+// nstep outside [1, 16], B * (stack + nstep) > 8192, no reward, a reward or
+// return / discount / steps pointer that is not 4-byte aligned, gamma outside
+// [0, 1] or NaN.
 struct ReplayStackParams {
   int stack = 1, stride = 1;
   int64_t capacity = 0;
@@ -338,6 +369,13 @@ struct ReplayStackParams {
   const uint8_t* next_src[kMaxMeta] = {};
   uint8_t* next_dst[kMaxMeta] = {};
   int next_bytes[kMaxMeta] = {};
+  int nstep = 0;                       // 0: 1-step transitions (off)
+  float gamma = 1.f;
+  const float* reward = nullptr;       // fp32 [capacity]
+  const uint8_t* done = nullptr;       // nullable, u8 [capacity]
+  float* return_out = nullptr;         // nullable, fp32 [B]
+  float* discount_out = nullptr;       // nullable, fp32 [B]
+  int32_t* steps_out = nullptr;        // nullable, int32 [B]
 };
 hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                                const ReplayStackParams& t, hipStream_t stream);

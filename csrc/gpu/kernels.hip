@@ -2006,7 +2006,9 @@ hipError_t replay_sample_crop(const DecodeParams& p, const ReplayParams& r, cons
 // virtual image v = (d * B + b) * k + f is frame e[b][f + d] through window
 // win[d * B + b], and lands at v * Cout * h * w of the dense output -- which is
 // [2, B, k * Cout, h, w].  The block prologue builds the frame table and the
-// windows in dynamic LDS: 4 * (B * (k + 1) + 2 B) bytes.
+// windows in dynamic LDS: 4 * (B * (k + 1) + 2 B) bytes; with n-step returns
+// (t.nstep = n) the table rows widen to k + n and a step offset per image joins
+// them: 4 * (B * (k + n) + 3 B) bytes.
 // Measured against the plain cropped sample of the same 2 B k images
 // (profiles/r14/replay_stack.md; 640x480 RGBA, pad 4, k = 3, fp32): batch 64
 // 340 against 334 us, batch 8 58.3 against 48.9 us -- the prologue's two
@@ -2018,13 +2020,36 @@ namespace {
 // s in [-cap, 2 cap) -> [0, cap)
 __device__ __forceinline__ int64_t ring_wrap(int64_t s, int64_t cap) { return s < 0 ? s + cap : (s >= cap ? s - cap : s); }
 
-// Fills tbl [B][k + 1] and win [2][B] (block 0 also the outputs); the caller
-// syncs.  The `first` flags are loaded in groups whose addresses do not
-// depend on each other: the four candidates of a Philox block, then the
-// slots the walk back may stop at; only the stop position follows them.
+// One fp32 product / sum, rounded to nearest on its own.  HIP's __fmul_rn and
+// __fadd_rn are the plain operators, which the compiler contracts into one FMA
+// (one rounding) under the default -ffp-contract=fast: the n-step return has to
+// give the bits of a float32 loop on the host, so these two opt out.
+__device__ __forceinline__ float fmul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float fadd_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// Fills tbl [B][k + max(n, 1)], win [2][B] and, with n-step returns, stepo [B]
+// (block 0 also the outputs); the caller syncs.  The `first` flags are loaded
+// in groups whose addresses do not depend on each other: the four candidates
+// of a Philox block, then the slots the walk back may stop at; only the stop
+// position follows them.  The n-step walk forward reads first[c_2 .. c_n] and
+// done[c_0 .. c_{n-1}], slots that depend on the anchor alone like the walk
+// back's: its first four steps are issued ahead of the walk back's loads and
+// read after them, so n <= 4 adds no load round at all.
+// NS: n-step returns.  The 1-step launch is its own instantiation: with the
+// walk behind a run-time branch it measured 2 % (batch 64) and 6 % (batch 8)
+// slower than before the walk existed (profiles/r16/replay_nstep.md).
+template <bool NS>
 __device__ __forceinline__ void stack_table(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
-                                            const ReplayStackParams& t, uint64_t ctr, uint32_t* tbl, uint32_t* win) {
-  const int k = t.stack, S = t.stride, B = p.B;
+                                            const ReplayStackParams& t, uint64_t ctr, uint32_t* tbl, uint32_t* win,
+                                            uint32_t* stepo) {
+  const int k = t.stack, S = t.stride, B = p.B, n = NS ? t.nstep : 0;
+  const int k1 = k + (n > 1 ? n : 1);
   const int64_t cap = t.capacity;
   // a device state was not seen by the host: reduced into the ring
   int64_t head = t.state ? t.state[0] : t.head, size = t.state ? t.state[1] : t.size;
@@ -2045,25 +2070,47 @@ __device__ __forceinline__ void stack_table(const DecodeParams& p, const ReplayP
       for (int blk = 0; blk < 4 && !valid; ++blk) {
         uint32_t o[4];
         philox_block(r.seed, ctr, uint32_t(b), blk ? uint32_t(blk + 1) : 0u, o);
-        int64_t s[4], n[4];
+        int64_t s[4], nx[4];
         uint8_t f[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           s[u] = ring_wrap(head - 1 - (int64_t(S) + __umulhi(o[u], range)), cap);
-          n[u] = ring_wrap(s[u] + S, cap);
+          nx[u] = ring_wrap(s[u] + S, cap);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) f[u] = t.first[n[u]];
+        for (int u = 0; u < 4; ++u) f[u] = t.first[nx[u]];
         anchor = s[3];   // none valid: the block's last candidate
 #pragma unroll
         for (int u = 3; u >= 0; --u)
-          if (f[u] == 0) anchor = s[u], succ = n[u], valid = true;
+          if (f[u] == 0) anchor = s[u], succ = nx[u], valid = true;
       }
       valid = valid && filled;
     }
     if (!valid) succ = anchor;
-    uint32_t* e = tbl + b * (k + 1);
-    e[k] = uint32_t(succ), e[k - 1] = uint32_t(anchor);
+    uint32_t* e = tbl + b * k1;
+    e[k - 1] = uint32_t(anchor);
+    if constexpr (!NS) e[k] = uint32_t(succ);
+    // n-step: bit j of dmask: done[c_j] != 0 (j < n); bit j of fmask:
+    // first[c_j] != 0 (2 <= j <= n).  Step j of a group reads done[c_j] and
+    // first[c_{j + 2}]; steps past n - 1 repeat it (their bits are dropped).
+    uint32_t dmask = 0, fmask = 0;
+    uint8_t gd[4] = {0, 0, 0, 0}, gf[4] = {0, 0, 0, 0};
+    int64_t fwd = anchor;   // c_j of the next forward step
+    if constexpr (NS) {
+      int64_t a[4], a2[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (u > 0 && u < n) fwd = ring_wrap(fwd + S, cap);
+        a[u] = fwd;
+        a2[u] = ring_wrap(ring_wrap(fwd + S, cap) + S, cap);
+      }
+      if (t.done) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gd[u] = t.done[a[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) gf[u] = t.first[a2[u]];
+    }
     // walk back: slot c_m = anchor - m S, m < k - 1, stops the walk when it is
     // a first frame or the oldest stored one; stopping is final, so the flags
     // of all c_m are read at once (indices past k - 2 repeat the last)
@@ -2092,6 +2139,49 @@ __device__ __forceinline__ void stack_table(const DecodeParams& p, const ReplayP
       if (m <= mstop) s = ring_wrap(s - S, cap);
       e[k - 1 - m] = uint32_t(s);
     }
+    int steps = 0;
+    bool terminated = false;
+    if constexpr (NS) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (u < n && gd[u] != 0) dmask |= 1u << u;
+        if (u + 2 <= n && gf[u] != 0) fmask |= 1u << (u + 2);
+      }
+      for (int j0 = 4; j0 < n; j0 += 4) {   // n > 4: further groups, still anchor-only addresses
+        int64_t a[4], a2[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (j0 + u < n) fwd = ring_wrap(fwd + S, cap);
+          a[u] = fwd;
+          a2[u] = ring_wrap(ring_wrap(fwd + S, cap) + S, cap);
+        }
+        if (t.done) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) gd[u] = t.done[a[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gf[u] = t.first[a2[u]];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (j0 + u < n && gd[u] != 0) dmask |= 1u << (j0 + u);
+          if (j0 + u + 2 <= n && gf[u] != 0) fmask |= 1u << (j0 + u + 2);
+        }
+      }
+      if (valid) {
+        steps = 1;
+        while (steps < n && ((dmask >> (steps - 1)) & 1u) == 0 && age0 - int64_t(steps) * S >= S &&
+               ((fmask >> (steps + 1)) & 1u) == 0)
+          ++steps;
+        terminated = ((dmask >> (steps - 1)) & 1u) != 0;
+      }
+      // e[k - 1 + j] = c_min(j, m); succ becomes c_m
+      succ = anchor;
+      for (int j = 1; j <= n; ++j) {
+        if (j <= steps) succ = ring_wrap(succ + S, cap);
+        e[k - 1 + j] = uint32_t(succ);
+      }
+      stepo[b] = uint32_t(steps > 1 ? steps : 1);
+    }
     const uint32_t w0 = replay_window(p, c, ctr, b, 1u);
     const uint32_t w1 = t.shared_window ? w0 : replay_window(p, c, ctr, b, 5u);
     win[b] = w0, win[B + b] = w1;
@@ -2108,6 +2198,32 @@ __device__ __forceinline__ void stack_table(const DecodeParams& p, const ReplayP
         t.next_crop_out[3 * b] = int(w1 & 0x7FFFu) - c.pad;
         t.next_crop_out[3 * b + 1] = int((w1 >> 15) & 0x7FFFu) - c.pad;
         t.next_crop_out[3 * b + 2] = int(w1 >> 31);
+      }
+      if constexpr (NS) {
+        // the rewards of c_0 .. c_{m-1}: independent loads, four at a time;
+        // every product and sum rounded on its own (no FMA)
+        float g = 1.f, R = 0.f;
+        int64_t q = anchor;
+        for (int j0 = 0; j0 < steps; j0 += 4) {
+          float rw[4];
+          int64_t a[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (j0 + u > 0 && j0 + u < steps) q = ring_wrap(q + S, cap);
+            a[u] = q;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) rw[u] = t.reward[a[u]];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (j0 + u < steps) {
+              R = fadd_rn(R, fmul_rn(g, rw[u]));
+              g = fmul_rn(g, t.gamma);
+            }
+        }
+        if (t.return_out) t.return_out[b] = R;
+        if (t.discount_out) t.discount_out[b] = (terminated || !valid) ? 0.f : g;
+        if (t.steps_out) t.steps_out[b] = steps;
       }
     }
   }
@@ -2133,33 +2249,42 @@ __device__ __forceinline__ void stack_meta_cols(int n, const uint8_t* const* src
   }
 }
 
-// anchor columns (r.meta_*, from e[k - 1]) first, then the next columns (from e[k])
+// anchor columns (r.meta_*, from e[k - 1]) first, then the next columns (from the
+// row's last entry: e[k], with n-step returns e[k - 1 + n] = c_m)
+template <bool NS>
 __device__ __forceinline__ void stack_meta(const ReplayParams& r, const ReplayStackParams& t, const uint32_t* tbl, int B,
                                            int64_t anchor_units, int64_t m) {
-  if (m < anchor_units) stack_meta_cols(r.nmeta, r.meta_src, r.meta_dst, r.meta_bytes, tbl, t.stack + 1, t.stack - 1, B, m);
-  else stack_meta_cols(t.nnext, t.next_src, t.next_dst, t.next_bytes, tbl, t.stack + 1, t.stack, B, m - anchor_units);
+  const int k1 = t.stack + (NS && t.nstep > 1 ? t.nstep : 1);
+  if (m < anchor_units) stack_meta_cols(r.nmeta, r.meta_src, r.meta_dst, r.meta_bytes, tbl, k1, t.stack - 1, B, m);
+  else stack_meta_cols(t.nnext, t.next_src, t.next_dst, t.next_bytes, tbl, k1, k1 - 1, B, m - anchor_units);
 }
 
-// virtual image v -> its frame slot and packed window
-__device__ __forceinline__ void stack_resolve(const uint32_t* tbl, const uint32_t* win, int B, int k, uint32_t v,
-                                              uint32_t& slot, uint32_t& w) {
+// virtual image v -> its frame slot and packed window.  stepo: the per-image
+// offset of the next stack in its table row (n-step returns; else it is 1)
+template <bool NS>
+__device__ __forceinline__ void stack_resolve(const uint32_t* tbl, const uint32_t* win, const uint32_t* stepo, int B,
+                                              int k, int k1, uint32_t v, uint32_t& slot, uint32_t& w) {
   const uint32_t Bk = uint32_t(B) * uint32_t(k);
   const uint32_t d = v >= Bk ? 1u : 0u;
   const uint32_t rem = v - d * Bk;
   const uint32_t b = rem / uint32_t(k), f = rem - b * uint32_t(k);
-  slot = tbl[b * uint32_t(k + 1) + f + d];
+  uint32_t off = d;
+  if constexpr (NS) off = d ? stepo[b] : 0u;
+  slot = tbl[b * uint32_t(k1) + f + off];
   w = win[d * uint32_t(B) + b];
 }
 
 // TBL / NT: replay_crop_vec_kernel's choices, inherited
-template <int PPT, int CIN, int OUTT, int TBL, bool NT = false>
+template <int PPT, int CIN, int OUTT, int TBL, bool NT = false, bool NS = false>
 __global__ __launch_bounds__(kBlock) void replay_stack_vec_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
                                                                   ReplayStackParams t, int64_t meta_units,
                                                                   int64_t anchor_units) {
   __shared__ uint32_t tab[kTabWords];
   extern __shared__ uint32_t stack_lds[];
+  const int k1 = t.stack + (NS && t.nstep > 1 ? t.nstep : 1);
   uint32_t* tbl = stack_lds;
-  uint32_t* win = stack_lds + p.B * (t.stack + 1);
+  uint32_t* win = stack_lds + p.B * k1;
+  uint32_t* stepo = win + 2 * p.B;   // NS only
   const int64_t hw = int64_t(c.h) * c.w;
   const int64_t groups_per_img = hw / PPT;
   const int64_t groups = groups_per_img * 2 * p.B * t.stack;
@@ -2171,18 +2296,18 @@ __global__ __launch_bounds__(kBlock) void replay_stack_vec_kernel(DecodeParams p
   const bool small = groups + meta_units + stride < (int64_t(1) << 31);
   const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
   const Xf xf = stage_xf(p.lut, tab, p.Cout);
-  stack_table(p, r, c, t, ctr, tbl, win);
+  stack_table<NS>(p, r, c, t, ctr, tbl, win, stepo);
   __syncthreads();
   for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < groups + meta_units; g += stride) {
     if (g >= groups) {
-      stack_meta(r, t, tbl, p.B, anchor_units, g - groups);
+      stack_meta<NS>(r, t, tbl, p.B, anchor_units, g - groups);
       continue;
     }
     Group gr;
     int i, j;
     split_group<PPT>(g, groups_per_img, c.w, small, gr.b, gr.q, i, j);
     uint32_t slot, w;
-    stack_resolve(tbl, win, p.B, t.stack, uint32_t(gr.b), slot, w);
+    stack_resolve<NS>(tbl, win, stepo, p.B, t.stack, k1, uint32_t(gr.b), slot, w);
     Pixels<PPT, CIN> px;
     if (load_crop_group<PPT, CIN>(p, r, c, int64_t(slot), w, i, j, px)) reverse_pixels<PPT, CIN>(px);
     emit<PPT, CIN, OUTT, NCHW, TBL, NT>(p, xf, cm, cout, hw, gr, px);
@@ -2190,31 +2315,33 @@ __global__ __launch_bounds__(kBlock) void replay_stack_vec_kernel(DecodeParams p
 }
 
 // any window size / alignment / channel count: one window pixel per lane
-template <int OUTT>
+template <int OUTT, bool NS = false>
 __global__ __launch_bounds__(kBlock) void replay_stack_scalar_kernel(DecodeParams p, ReplayParams r, ReplayCropParams c,
                                                                      ReplayStackParams t, int64_t meta_units,
                                                                      int64_t anchor_units) {
   __shared__ uint32_t tab[kTabWords];
   extern __shared__ uint32_t stack_lds[];
+  const int k1 = t.stack + (NS && t.nstep > 1 ? t.nstep : 1);
   uint32_t* tbl = stack_lds;
-  uint32_t* wins = stack_lds + p.B * (t.stack + 1);
+  uint32_t* wins = stack_lds + p.B * k1;
+  uint32_t* stepo = wins + 2 * p.B;   // NS only
   const uint64_t ctr = r.counter ? r.counter[0] : r.ctr_value;
   const Xf xf = stage_xf(p.lut, tab, p.Cout);
-  stack_table(p, r, c, t, ctr, tbl, wins);
+  stack_table<NS>(p, r, c, t, ctr, tbl, wins, stepo);
   __syncthreads();
   const int64_t hw = int64_t(c.h) * c.w;
   const int64_t total = hw * 2 * p.B * t.stack;
   const int64_t ie = hw * p.Cout;
   for (int64_t g = int64_t(blockIdx.x) * kBlock + threadIdx.x; g < total + meta_units; g += int64_t(gridDim.x) * kBlock) {
     if (g >= total) {
-      stack_meta(r, t, tbl, p.B, anchor_units, g - total);
+      stack_meta<NS>(r, t, tbl, p.B, anchor_units, g - total);
       continue;
     }
     const int64_t v = g / hw;
     const int64_t q = g - v * hw;
     const int i = int(q / c.w), j = int(q - int64_t(i) * c.w);
     uint32_t slot, win;
-    stack_resolve(tbl, wins, p.B, t.stack, uint32_t(v), slot, win);
+    stack_resolve<NS>(tbl, wins, stepo, p.B, t.stack, k1, uint32_t(v), slot, win);
     const int y0 = int(win & 0x7FFFu) - c.pad, x0 = int((win >> 15) & 0x7FFFu) - c.pad;
     const int y = clampi(y0 + i, 0, p.H - 1);
     const int sy = p.flip_all ? p.H - 1 - y : y;
@@ -2231,7 +2358,7 @@ __global__ __launch_bounds__(kBlock) void replay_stack_scalar_kernel(DecodeParam
   }
 }
 
-template <int PPT, int CIN, int OUTT>
+template <int PPT, int CIN, int OUTT, bool NS>
 void launch_replay_stack_vec(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                              const ReplayStackParams& t, int64_t meta_units, int64_t anchor_units, int grid, size_t lds,
                              hipStream_t s) {
@@ -2239,21 +2366,23 @@ void launch_replay_stack_vec(const DecodeParams& p, const ReplayParams& r, const
     if (p.xf_table_only) {
       // non-temporal stores as in launch_replay_crop_vec (BT_REPLAY_CROP_NT=0: plain stores)
       static const bool nt = !(std::getenv("BT_REPLAY_CROP_NT") && std::getenv("BT_REPLAY_CROP_NT")[0] == '0');
-      if (nt) replay_stack_vec_kernel<PPT, CIN, OUTT, 1, true><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
-      else replay_stack_vec_kernel<PPT, CIN, OUTT, 1><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+      if (nt) replay_stack_vec_kernel<PPT, CIN, OUTT, 1, true, NS><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+      else replay_stack_vec_kernel<PPT, CIN, OUTT, 1, false, NS><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
       return;
     }
   }
-  if (p.xf_table_only) replay_stack_vec_kernel<PPT, CIN, OUTT, 1><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
-  else replay_stack_vec_kernel<PPT, CIN, OUTT, 0><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+  if (p.xf_table_only) replay_stack_vec_kernel<PPT, CIN, OUTT, 1, false, NS><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
+  else replay_stack_vec_kernel<PPT, CIN, OUTT, 0, false, NS><<<grid, kBlock, lds, s>>>(p, r, c, t, meta_units, anchor_units);
 }
 
-template <int OUTT>
+template <int OUTT, bool NS>
 hipError_t launch_replay_stack(const DecodeParams& p, const ReplayParams& r, const ReplayCropParams& c,
                                const ReplayStackParams& t, int64_t meta_units, int64_t anchor_units, hipStream_t s) {
   constexpr int PPT = ppt_for(OUTT);
   constexpr int64_t ELEM = elem_for(OUTT);
-  const size_t lds = sizeof(uint32_t) * (size_t(p.B) * size_t(t.stack + 1) + 2 * size_t(p.B));
+  // frame table [B][k + max(n, 1)], windows [2][B], with n-step returns the step offsets [B]
+  const size_t lds = sizeof(uint32_t) * (size_t(p.B) * size_t(t.stack + (t.nstep > 1 ? t.nstep : 1)) +
+                                         (t.nstep ? 3 : 2) * size_t(p.B));
   const int64_t pixels = int64_t(2) * p.B * t.stack * c.h * c.w;
   // launch_replay_crop's vector conditions
   const bool vec = (c.w % PPT) == 0 && (p.W % 4) == 0 && r.frame_bytes % 16 == 0 && (p.Cin == 3 || p.Cin == 4) &&
@@ -2261,10 +2390,10 @@ hipError_t launch_replay_stack(const DecodeParams& p, const ReplayParams& r, con
                    (int64_t(c.h) * c.w * p.Cout * ELEM) % 16 == 0;
   if (vec) {
     const int grid = grid_for(pixels / PPT + meta_units, p.max_grid);
-    if (p.Cin == 4) launch_replay_stack_vec<PPT, 4, OUTT>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
-    else launch_replay_stack_vec<PPT, 3, OUTT>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
+    if (p.Cin == 4) launch_replay_stack_vec<PPT, 4, OUTT, NS>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
+    else launch_replay_stack_vec<PPT, 3, OUTT, NS>(p, r, c, t, meta_units, anchor_units, grid, lds, s);
   } else {
-    replay_stack_scalar_kernel<OUTT><<<grid_for(pixels + meta_units, p.max_grid), kBlock, lds, s>>>(p, r, c, t, meta_units,
+    replay_stack_scalar_kernel<OUTT, NS><<<grid_for(pixels + meta_units, p.max_grid), kBlock, lds, s>>>(p, r, c, t, meta_units,
                                                                                                    anchor_units);
   }
   return hipGetLastError();
@@ -2297,6 +2426,13 @@ hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, con
     return hipErrorInvalidValue;
   if (!t.state && (t.size <= t.stride || t.size > t.capacity || t.head < 0 || t.head >= t.capacity))
     return hipErrorInvalidValue;
+  if (t.nstep != 0) {   // n-step returns: LDS stays 4 * (B (k + n) + 3 B) <= 44 KiB next to the value table
+    if (t.nstep < 1 || t.nstep > 16 || int64_t(p.B) * (t.stack + t.nstep) > 8192 || !t.reward) return hipErrorInvalidValue;
+    if (!(t.gamma >= 0.f && t.gamma <= 1.f)) return hipErrorInvalidValue;   // NaN fails both
+    if ((reinterpret_cast<uintptr_t>(t.reward) | reinterpret_cast<uintptr_t>(t.return_out) |
+         reinterpret_cast<uintptr_t>(t.discount_out) | reinterpret_cast<uintptr_t>(t.steps_out)) % 4)
+      return hipErrorInvalidValue;
+  }
   ReplayCropParams c = c0;
   if (c.h == 0 && c.w == 0) {   // no crop: the whole frame at (0, 0)
     c = ReplayCropParams();
@@ -2326,8 +2462,10 @@ hipError_t replay_sample_stack(const DecodeParams& p, const ReplayParams& r, con
   c.ny = uint32_t(p.H + 2 * c.pad - c.h + 1);
   c.nx = uint32_t((p.W + 2 * c.pad - c.w) / c.x_align + 1);
   const int64_t meta_units = anchor_units + next_units;
-  const hipError_t e = with_out_dtype(
-      p.out_dtype, [&](auto o) { return launch_replay_stack<o()>(p, r, c, t, meta_units, anchor_units, stream); });
+  const hipError_t e = with_out_dtype(p.out_dtype, [&](auto o) {
+    return t.nstep ? launch_replay_stack<o(), true>(p, r, c, t, meta_units, anchor_units, stream)
+                   : launch_replay_stack<o(), false>(p, r, c, t, meta_units, anchor_units, stream);
+  });
   // a device counter moves on when this launch drew from it: anchors, or windows
   const bool drew = !r.index_in || c.mode == kCropRandom;
   if (e != hipSuccess || !r.counter || !drew) return e;

@@ -488,7 +488,8 @@ PYBIND11_MODULE(_hip, m) {
            std::vector<uintptr_t> next_src, std::vector<uintptr_t> next_dst, std::vector<int> next_bytes,
            uintptr_t stream, int xf_table_only, int max_grid, std::vector<int> crop_size, std::string crop_mode,
            std::vector<int> crop_origin, int crop_pad, double mirror, int x_align, uint64_t window_key,
-           int shared_window, uintptr_t crop_out, uintptr_t next_crop_out) {
+           int shared_window, uintptr_t crop_out, uintptr_t next_crop_out, int nstep, double gamma, uintptr_t reward,
+           uintptr_t done, uintptr_t return_out, uintptr_t discount_out, uintptr_t steps_out) {
           DecodeParams p;
           p.xf_table_only = xf_table_only;
           p.max_grid = max_grid;
@@ -516,6 +517,14 @@ PYBIND11_MODULE(_hip, m) {
           t.next_index_out = ptr<int64_t>(next_index_out);
           t.valid_out = ptr<uint8_t>(valid_out);
           t.next_crop_out = ptr<int32_t>(next_crop_out);
+          // n-step returns (nstep = 0: off); a gamma outside [0, 1] stays outside as fp32 and is refused below
+          t.nstep = nstep;
+          t.gamma = float(gamma);
+          t.reward = ptr<const float>(reward);
+          t.done = ptr<const uint8_t>(done);
+          t.return_out = ptr<float>(return_out);
+          t.discount_out = ptr<float>(discount_out);
+          t.steps_out = ptr<int32_t>(steps_out);
           if (meta_src.size() != meta_dst.size() || meta_src.size() != meta_bytes.size() ||
               meta_src.size() > size_t(kMaxMeta) || next_src.size() != next_dst.size() ||
               next_src.size() != next_bytes.size() || next_src.size() > size_t(kMaxMeta))
@@ -567,7 +576,10 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("xf_table_only") = 0, py::arg("max_grid") = 0, py::arg("crop_size") = std::vector<int>(),
         py::arg("crop_mode") = "random", py::arg("crop_origin") = std::vector<int>(), py::arg("crop_pad") = 0,
         py::arg("mirror") = 0.0, py::arg("x_align") = 1, py::arg("window_key") = uint64_t(0),
-        py::arg("shared_window") = 0, py::arg("crop_out") = uintptr_t(0), py::arg("next_crop_out") = uintptr_t(0));
+        py::arg("shared_window") = 0, py::arg("crop_out") = uintptr_t(0), py::arg("next_crop_out") = uintptr_t(0),
+        py::arg("nstep") = 0, py::arg("gamma") = 1.0, py::arg("reward") = uintptr_t(0), py::arg("done") = uintptr_t(0),
+        py::arg("return_out") = uintptr_t(0), py::arg("discount_out") = uintptr_t(0),
+        py::arg("steps_out") = uintptr_t(0));
 
   m.def("multi_cast",
         [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst, std::vector<int64_t> numel, int mode,

@@ -28,7 +28,9 @@ epoch after the first then runs at HBM speed without touching the host:
 * ``sample_transitions(B, decode, stack=k, stride=S)``: frame-stacked
   transitions for pixel-based RL (``obs``, ``next_obs``, the metadata at both
   ends) assembled by the sample kernel from frames stored once; episode
-  starts come from a one-byte ``first`` metadata column.
+  starts come from a one-byte ``first`` metadata column.  ``nstep=n,
+  gamma=g`` adds the n-step return, its bootstrap discount and the stack n
+  steps later, in the same launch.
 
 On a CPU device the same API runs with the fp32 reference ops (tests, hosts
 without a GPU). On a GPU device the HIP kernels are required and fail loudly
@@ -389,7 +391,8 @@ class DeviceReplayBuffer:
         return replay
 
     # -- frame-stacked transitions ------------------------------------------------
-    def _transitions(self, B, idx, decode, stack, stride, first_key, next_keys, shared_window, _counter):
+    def _transitions(self, B, idx, decode, stack, stride, first_key, next_keys, shared_window, _counter,
+                     nstep=None, gamma=0.99, reward_key='reward', done_key=None):
         if self._size == 0:
             raise IndexError('empty replay buffer')
         ops._transition_cfg(decode, 'DeviceReplayBuffer transitions')
@@ -408,6 +411,19 @@ class DeviceReplayBuffer:
             raise ValueError('stride must lie in [1, capacity)')
         if self._size <= stride:
             raise ValueError(f'transitions need more than stride = {stride} stored frames: {self._size}')
+        reward = done = None
+        if nstep is not None:
+            nstep, _ = ops._nstep_args(nstep, gamma)
+            if B * (stack + nstep) > ops.MAX_STACK_TABLE:
+                raise ValueError(f'n-step transitions need batch * (stack + nstep) <= {ops.MAX_STACK_TABLE}')
+            reward = self.meta.get(reward_key)
+            if reward is None or reward.dim() != 1 or reward.dtype != torch.float32:
+                raise ValueError(f'n-step returns need a float32 [capacity] metadata column {reward_key!r} '
+                                 '(the reward of the step taken from each frame)')
+            if done_key is not None:
+                done = self.meta.get(done_key)
+                if done is None or done.dim() != 1 or done.dtype not in (torch.uint8, torch.bool):
+                    raise ValueError(f'done_key: no uint8 / bool [capacity] metadata column {done_key!r}')
         crop = decode.crop
         ctr = _counter
         if ctr is None:
@@ -420,19 +436,24 @@ class DeviceReplayBuffer:
             out, info = ops.replay_transitions(
                 self.store, self._next, self._size, B, decode, stack=stack, stride=stride, first=first, seed=self.seed,
                 counter=ctr, index=idx, meta=self.meta, next_meta={k: self.meta[k] for k in next_keys},
-                shared_window=shared_window, state=self._state if isinstance(ctr, torch.Tensor) else None)
+                shared_window=shared_window, state=self._state if isinstance(ctr, torch.Tensor) else None,
+                nstep=nstep, gamma=gamma, reward=reward, done=done)
             batch = {'obs': out[0], 'next_obs': out[1], **info['meta']}
             batch.update({'next_' + k: v for k, v in info['next_meta'].items()})
             batch.update(index=info['index'], next_index=info['next_index'], valid=info['valid'])
             if crop is not None:
                 batch.update(crop=info['crop'], next_crop=info['next_crop'])
+            if nstep is not None:
+                batch.update({k: info[k] for k in ('nstep_return', 'nstep_discount', 'nstep_steps')})
             return batch
         # the reference path: the numpy references of the kernel's draws + reference_decode
         ring = (self._next, self._size, self.capacity, stride, stack, first.numpy())
+        nkw = {} if nstep is None else dict(nstep=nstep, done=None if done is None else done.numpy())
         if idx is None:
-            anchor, succ, table, valid = ops.philox_transitions(self.seed, ctr, B, *ring)
+            anchor, succ, table, valid = ops.philox_transitions(self.seed, ctr, B, *ring, **nkw)
         else:
-            anchor, succ, table, valid = ops.given_transitions(idx.cpu().numpy(), *ring)
+            anchor, succ, table, valid = ops.given_transitions(idx.cpu().numpy(), *ring, **nkw)
+        tables = (table[:, :stack], table[:, 1:]) if nstep is None else table
         H, W = self.frame_shape[:2]
         wins = None
         if crop is not None:
@@ -440,7 +461,7 @@ class DeviceReplayBuffer:
             wins = ops.transition_windows(crop, H, W, B, seed=self.seed, counter=ctr, shared_window=shared_window)
         sides = []
         for d in (0, 1):
-            planes = [ops.reference_decode(self.store.index_select(0, torch.from_numpy(table[:, f + d])), decode,
+            planes = [ops.reference_decode(self.store.index_select(0, torch.from_numpy(tables[d][:, f].copy())), decode,
                                            crop=None if wins is None else wins[d]) for f in range(stack)]
             sides.append(torch.cat(planes, dim=1))
         anchor, succ = torch.from_numpy(anchor), torch.from_numpy(succ)
@@ -450,11 +471,17 @@ class DeviceReplayBuffer:
         batch.update(index=anchor, next_index=succ, valid=torch.from_numpy(valid))
         if wins is not None:
             batch.update(crop=torch.from_numpy(wins[0].copy()), next_crop=torch.from_numpy(wins[1].copy()))
+        if nstep is not None:
+            _, steps, ret, disc = ops.nstep_transitions(anchor.numpy(), valid, self._next, self._size, self.capacity,
+                                                        stride, nstep, gamma, reward.numpy(), first.numpy(),
+                                                        done=nkw['done'])
+            batch.update(nstep_return=torch.from_numpy(ret), nstep_discount=torch.from_numpy(disc),
+                         nstep_steps=torch.from_numpy(steps))
         return batch
 
     def sample_transitions(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                            stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
-                           _counter=None):
+                           _counter=None, nstep=None, gamma: float = 0.99, reward_key: str = 'reward', done_key=None):
         """A batch of frame-stacked transitions out of the frame-once store.
 
         Storage convention (nothing about ``extend`` changes): an RL loop
@@ -484,24 +511,45 @@ class DeviceReplayBuffer:
         launch (``ops.replay_transitions``); a CPU buffer with the same seed
         and call sequence returns the same batches.  Colour-kernel, resize
         and NHWC configs raise ``ValueError`` (NHWC: channel-stacked
-        channels-last output needs another store pattern)."""
+        channels-last output needs another store pattern).
+
+        ``nstep`` = n in [1, 16] makes them n-step transitions, still in the
+        one launch.  Storage convention: the float32 column ``reward_key``
+        holds at each frame the reward of the step taken FROM it, and the
+        optional uint8 / bool column ``done_key`` is non-zero where that step
+        terminated the episode; terminal observations are stored as frames
+        (the frame after one is a ``first`` frame).  From each anchor the
+        walk takes m <= n steps, stopping at the episode's end and at the
+        newest stored step.  ``next_obs``, ``next_index`` and the
+        ``'next_' + key`` columns are then taken m steps after the anchor,
+        and the batch also holds ``nstep_return`` (float32: ``r_t + gamma
+        r_{t+1} + ... + gamma^(m-1) r_{t+m-1}``), ``nstep_discount``
+        (float32: ``gamma^m``, the factor of the bootstrap term) and
+        ``nstep_steps`` (int32: m; 0 where ``valid`` is False).  With a done
+        column ``nstep_discount`` is 0 after a termination: the target is
+        ``nstep_return + nstep_discount * Q(next_obs)`` with no further
+        mask.  Without one the walk merely truncates at the episode's end
+        (time-limit semantics: the last observation still bootstraps).
+        ``index`` and ``valid`` are the 1-step ones whatever ``nstep`` is;
+        ``ops.nstep_transitions`` is the reference."""
         return self._transitions(int(batch_size), None, decode, stack, stride, first_key, next_keys, shared_window,
-                                 _counter)
+                                 _counter, nstep, gamma, reward_key, done_key)
 
     def gather_transitions(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                            stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
-                           _counter=None):
+                           _counter=None, nstep=None, gamma: float = 0.99, reward_key: str = 'reward', done_key=None):
         """:meth:`sample_transitions` at given anchors ``idx`` (slots).
         ``valid`` is False where the anchor is among the newest ``stride``
         frames, is not stored, or its successor is a ``first`` frame.  A random
         crop draws its windows at the buffer's Philox counter."""
         idx = idx.to(self.device, torch.int64).reshape(-1)
         return self._transitions(int(idx.numel()), idx, decode, stack, stride, first_key, next_keys, shared_window,
-                                 _counter)
+                                 _counter, nstep, gamma, reward_key, done_key)
 
     def graphed_transition_sampler(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                                    stride: int = 1, first_key: str = 'first', next_keys=(),
-                                   shared_window: bool = False, warmup: int = 3):
+                                   shared_window: bool = False, warmup: int = 3, nstep=None, gamma: float = 0.99,
+                                   reward_key: str = 'reward', done_key=None):
         """:meth:`sample_transitions` captured once as a HIP graph.  The
         Philox counter lives in device memory (as in :meth:`graphed_sampler`)
         and so does the ring state: the kernel reads ``(head, size)`` from a
@@ -509,7 +557,8 @@ class DeviceReplayBuffer:
         ONE capture serves a buffer that grows every environment step.  The
         returned callable replays the graph and returns the same static
         output dict every time."""
-        kw = dict(stack=stack, stride=stride, first_key=first_key, next_keys=next_keys, shared_window=shared_window)
+        kw = dict(stack=stack, stride=stride, first_key=first_key, next_keys=next_keys, shared_window=shared_window,
+                  nstep=nstep, gamma=gamma, reward_key=reward_key, done_key=done_key)
         if self.device.type != 'cuda':
             return lambda: self.sample_transitions(batch_size, decode, **kw)
         if self._state is None:

@@ -1336,7 +1336,8 @@ def replay_sample(store, count: int, batch: int, cfg: DecodeConfig = DecodeConfi
 # a slot is stored iff age < size.
 
 MAX_STACK = 16            # kernels.h: replay_sample_stack
-MAX_STACK_TABLE = 8192    # B * (stack + 1)
+MAX_STACK_TABLE = 8192    # B * (stack + 1); with n-step returns B * (stack + nstep)
+MAX_NSTEP = 16
 
 
 def _ring_args(head, size, capacity, stride, stack, first):
@@ -1368,8 +1369,96 @@ def _frame_table(anchor, succ, head, size, capacity, stride, stack, first):
     return e
 
 
+def _nstep_args(nstep, gamma):
+    nstep = int(nstep)
+    if not 1 <= nstep <= MAX_NSTEP:
+        raise ValueError(f'nstep must lie in [1, {MAX_NSTEP}]')
+    gamma = np.float32(gamma)
+    if not 0.0 <= float(gamma) <= 1.0:      # NaN fails both
+        raise ValueError('gamma must lie in [0, 1]')
+    return nstep, gamma
+
+
+def _nstep_steps(anchor, valid, head, size, capacity, stride, nstep, first, done):
+    """int64 [B] number of steps m and bool [B] terminated of :func:`nstep_transitions`."""
+    age0 = (head - 1 - anchor) % capacity
+    m = valid.astype(np.int64)
+    grow = valid.copy()
+    for step in range(1, nstep):                          # m = step -> step + 1 where every condition holds
+        if done is not None:
+            grow &= ~done[(anchor + (step - 1) * stride) % capacity]
+        grow &= age0 - step * stride >= stride            # c_{m+1} is stored
+        grow &= ~first[(anchor + (step + 1) * stride) % capacity]
+        m += grow
+    last = (anchor + np.maximum(m - 1, 0) * stride) % capacity
+    terminated = valid & done[last] if done is not None else np.zeros(len(anchor), bool)
+    return m, terminated
+
+
+def nstep_transitions(anchor, valid, head: int, size: int, capacity: int, stride: int, nstep: int, gamma: float,
+                      reward, first, done=None):
+    """The n-step walk of :func:`replay_transitions` (numpy reference):
+    ``(succ, steps, ret, discount)`` -- int64 [B], int32 [B], float32 [B],
+    float32 [B] -- for anchors ``anchor`` with 1-step validity ``valid``
+    (:func:`philox_transitions` / :func:`given_transitions`).
+
+    ``reward[s]`` (float32 [capacity]) is the reward of the step taken from
+    slot s; ``done[s] != 0`` (optional) means that step terminated the
+    episode.  With ``c_j = (anchor + j * stride) % capacity``:
+
+    * ``steps`` m is 0 for an invalid image.  Else it starts at 1 and grows
+      while ``m < nstep``, and (no ``done`` or ``done[c_{m-1}] == 0``), and
+      ``c_{m+1}`` is stored (``age(anchor) - m * stride >= stride``), and
+      ``first[c_{m+1}] == 0``: the walk stops at an episode end and at the
+      newest stored step.
+    * ``ret``: ``g = 1; R = 0; for j < m: R = R + g * reward[c_j]; g = g * gamma``,
+      every product and sum rounded to float32 on its own -- the kernel uses
+      no FMA, so the bits agree.
+    * ``discount``: ``g`` after the loop (``gamma ** m``); 0 for an invalid
+      image and after a termination (``done[c_{m-1}] != 0``): the bootstrap
+      term vanishes.
+    * ``succ`` = ``c_m``, the slot to bootstrap from (the anchor if invalid)."""
+    head, size, capacity, stride, _, first = _ring_args(head, size, capacity, stride, 1, first)
+    nstep, gamma = _nstep_args(nstep, gamma)
+    anchor = np.asarray(anchor, np.int64).reshape(-1) % capacity
+    valid = np.asarray(valid).reshape(-1) != 0
+    reward = np.asarray(reward)
+    if reward.dtype != np.float32 or reward.shape != (capacity,):
+        raise ValueError(f'reward must be float32 [{capacity}]')
+    if done is not None:
+        done = np.asarray(done)
+        if done.dtype not in (np.uint8, np.bool_) or done.shape != (capacity,):
+            raise ValueError(f'done must be uint8 / bool [{capacity}]')
+        done = done != 0
+    m, terminated = _nstep_steps(anchor, valid, head, size, capacity, stride, nstep, first, done)
+    g, ret = np.ones(len(anchor), np.float32), np.zeros(len(anchor), np.float32)
+    with np.errstate(all='ignore'):
+        for j in range(nstep):
+            on = j < m
+            term = (g * reward[(anchor + j * stride) % capacity]).astype(np.float32)
+            ret = np.where(on, (ret + term).astype(np.float32), ret)
+            g = np.where(on, (g * gamma).astype(np.float32), g)
+    discount = np.where(terminated | ~valid, np.float32(0), g).astype(np.float32)
+    return (anchor + m * stride) % capacity, m.astype(np.int32), ret, discount
+
+
+def _nstep_tables(anchor, table, valid, head, size, capacity, stride, stack, nstep, first, done):
+    """``(succ, (obs_table, next_table))`` of an n-step sample: both [B, stack], the next stack the walk back
+    from c_m (an invalid image: today's ``table[:, 1:]``)."""
+    nstep, _ = _nstep_args(nstep, 0.0)
+    if done is not None:
+        done = np.asarray(done).reshape(-1) != 0
+        if done.shape[0] != capacity:
+            raise ValueError(f'done must hold one flag per slot ({capacity})')
+    m, _ = _nstep_steps(anchor, valid, head, size, capacity, stride, nstep, first, done)
+    succ = (anchor + m * stride) % capacity
+    nxt = _frame_table(succ, succ, head, size, capacity, stride, stack, first)[:, :stack]
+    nxt[~valid] = table[~valid, 1:]
+    return succ, (table[:, :stack].copy(), nxt)
+
+
 def philox_transitions(seed: int, counter: int, B: int, head: int, size: int, capacity: int, stride: int, stack: int,
-                       first):
+                       first, nstep=None, done=None):
     """The transitions :func:`replay_transitions` draws (numpy reference):
     ``(anchors, successors, table, valid)`` -- int64 [B], int64 [B], int64
     [B, stack + 1] and bool [B].
@@ -1391,7 +1480,13 @@ def philox_transitions(seed: int, counter: int, B: int, head: int, size: int, ca
     then the successor: walking back by ``stride`` from the anchor, the walk
     stays where it is on a ``first`` frame (the episode's first frame
     repeats) and on the oldest stored frame.  The observation stack is
-    ``table[:, :stack]``, the next one ``table[:, 1:]``."""
+    ``table[:, :stack]``, the next one ``table[:, 1:]``.
+
+    With ``nstep`` (and the optional ``done`` column) the successor is the
+    n-step one, ``c_m`` of :func:`nstep_transitions`, and ``table`` becomes
+    the pair ``(obs_table, next_table)``, int64 [B, stack] each: the next
+    stack is the ``stack`` frames ending at ``c_m``.  Anchors and ``valid``
+    do not depend on ``nstep``."""
     head, size, capacity, stride, stack, first = _ring_args(head, size, capacity, stride, stack, first)
     anchor, succ = np.zeros(B, np.int64), np.zeros(B, np.int64)
     valid = np.zeros(B, bool)
@@ -1407,20 +1502,28 @@ def philox_transitions(seed: int, counter: int, B: int, head: int, size: int, ca
             valid |= take
     anchor[~valid] = s[~valid]
     succ[~valid] = anchor[~valid]
-    return anchor, succ, _frame_table(anchor, succ, head, size, capacity, stride, stack, first), valid
+    table = _frame_table(anchor, succ, head, size, capacity, stride, stack, first)
+    if nstep is not None:
+        succ, table = _nstep_tables(anchor, table, valid, head, size, capacity, stride, stack, nstep, first, done)
+    return anchor, succ, table, valid
 
 
-def given_transitions(index, head: int, size: int, capacity: int, stride: int, stack: int, first):
+def given_transitions(index, head: int, size: int, capacity: int, stride: int, stack: int, first, nstep=None,
+                      done=None):
     """:func:`philox_transitions` for given anchors ``index`` (reduced mod
     ``capacity``): valid iff ``stride <= age(anchor) < size`` and the successor
-    is no ``first`` frame; an invalid image has ``successor = anchor``."""
+    is no ``first`` frame; an invalid image has ``successor = anchor``.
+    ``nstep`` / ``done`` as in :func:`philox_transitions`."""
     head, size, capacity, stride, stack, first = _ring_args(head, size, capacity, stride, stack, first)
     anchor = np.asarray(index, np.int64).reshape(-1) % capacity
     succ = (anchor + stride) % capacity
     age = (head - 1 - anchor) % capacity
     valid = (age >= stride) & (age < size) & ~first[succ]
     succ = np.where(valid, succ, anchor)
-    return anchor, succ, _frame_table(anchor, succ, head, size, capacity, stride, stack, first), valid
+    table = _frame_table(anchor, succ, head, size, capacity, stride, stack, first)
+    if nstep is not None:
+        succ, table = _nstep_tables(anchor, table, valid, head, size, capacity, stride, stack, nstep, first, done)
+    return anchor, succ, table, valid
 
 
 def transition_windows(crop: Crop, H: int, W: int, B: int, seed: int = 0, counter: int = 0, shared_window=False):
@@ -1447,7 +1550,8 @@ def _transition_cfg(cfg, where):
 
 def replay_transitions(store, head: int, size: int, batch: int, cfg: DecodeConfig = DecodeConfig(), stack: int = 1,
                        stride: int = 1, first=None, seed: int = 0, counter=None, index=None, meta=None,
-                       next_meta=None, shared_window: bool = False, state=None):
+                       next_meta=None, shared_window: bool = False, state=None, nstep=None, gamma: float = 0.99,
+                       reward=None, done=None):
     """Frame-stacked transitions out of a frame-once store, in ONE launch of
     the gfx950 kernel: ``(stacks, info)``.
 
@@ -1475,6 +1579,20 @@ def replay_transitions(store, head: int, size: int, batch: int, cfg: DecodeConfi
     ``counter`` as in :func:`replay_sample`.  ``state``: a device int64 [2]
     holding (head, size), read by the kernel instead of the arguments -- a
     captured graph then follows a store that grows between replays.
+
+    ``nstep`` = n in [1, 16]: multi-step returns in the same launch
+    (:func:`nstep_transitions` has the contract).  ``reward`` (contiguous
+    float32 [capacity]; ``reward[s]`` the reward of the step taken from slot
+    s) and the optional ``done`` (uint8 / bool [capacity]; that step
+    terminated the episode) are walked forward from the anchor for up to n
+    steps, stopping at an episode end and at the newest stored step.
+    ``stacks[1]`` is then the stack ending m steps after the anchor,
+    ``next_index`` / ``next_meta`` are taken there, and ``info`` also holds
+    ``nstep_return`` (float32: the discounted reward sum, separately rounded
+    fp32 products and sums), ``nstep_discount`` (float32: ``gamma ** m``, 0
+    after a termination or for an invalid image) and ``nstep_steps`` (int32:
+    m).  ``index`` and ``valid`` do not depend on ``nstep``; ``nstep=None``
+    is the 1-step launch, byte for byte.
 
     Only NCHW output: channel-stacked NHWC needs another store pattern."""
     import torch
@@ -1541,12 +1659,28 @@ def replay_transitions(store, head: int, size: int, batch: int, cfg: DecodeConfi
         return mout, src, dst, nbytes
     info['meta'], src, dst, nbytes = columns(meta)
     info['next_meta'], nsrc, ndst, nnbytes = columns(next_meta)
+    nkw = {}
+    if nstep is not None:
+        _nstep_args(nstep, gamma)
+        if reward is None or not isinstance(reward, torch.Tensor) or reward.device != dev \
+                or reward.dtype != torch.float32 or tuple(reward.shape) != (N,) or not reward.is_contiguous():
+            raise ValueError(f'n-step returns need a contiguous float32 [{N}] reward column on {dev}')
+        if done is not None and (not isinstance(done, torch.Tensor) or done.device != dev
+                                 or done.dtype not in (torch.uint8, torch.bool) or tuple(done.shape) != (N,)
+                                 or not done.is_contiguous()):
+            raise ValueError(f'done must be a contiguous uint8 / bool [{N}] tensor on {dev}')
+        info['nstep_return'] = torch.empty(batch, dtype=torch.float32, device=dev)
+        info['nstep_discount'] = torch.empty(batch, dtype=torch.float32, device=dev)
+        info['nstep_steps'] = torch.empty(batch, dtype=torch.int32, device=dev)
+        nkw = dict(nstep=int(nstep), gamma=float(gamma), reward=reward.data_ptr(),
+                   done=0 if done is None else done.data_ptr(), return_out=info['nstep_return'].data_ptr(),
+                   discount_out=info['nstep_discount'].data_ptr(), steps_out=info['nstep_steps'].data_ptr())
     lut = device_lut(cfg, dev)
     ext.replay_transitions(store.data_ptr(), N, int(head), int(size), state_ptr, first.data_ptr(), int(stack),
                            int(stride), out.data_ptr(), lut.data_ptr(), batch, H, W, C, cfg.cout, cfg.cmap,
                            int(cfg.flip), OUT_DTYPES[cfg.dtype], LAYOUTS[cfg.layout], int(seed) & (2 ** 64 - 1),
                            ctr_ptr, ctr_value, idx_in, idx_out.data_ptr(), nidx_out.data_ptr(), valid.data_ptr(),
-                           src, dst, nbytes, nsrc, ndst, nnbytes, _stream(dev), table_only(cfg, dev), **ckw)
+                           src, dst, nbytes, nsrc, ndst, nnbytes, _stream(dev), table_only(cfg, dev), **ckw, **nkw)
     info.update(index=idx_out, next_index=nidx_out, valid=valid)
     return out, info
 
