@@ -550,9 +550,13 @@ void StreamLoader::run() {
       // with copies in flight, wake up often enough to recycle their slots
       // promptly (producers / IO threads may be waiting for them)
       trace::Range tp("btn.loader.poll");
-      ev = zmtp::Socket::poll(items, inflight_.empty() && pending_.empty() && unready_.empty() ? 100 : (unready_.empty() ? 1 : 0),
+      // batches held behind queued launches (launch_policy.h) leave when one
+      // retires: like a completion, that is polled for, never slept through
+      const bool held = !pending_.empty() && !inflight_.empty();
+      const bool watch = held || !unready_.empty();
+      ev = zmtp::Socket::poll(items, inflight_.empty() && pending_.empty() && unready_.empty() ? 100 : (watch ? 0 : 1),
                               intr);
-      if (!unready_.empty() && std::none_of(ev.begin(), ev.end(), [](int e) { return e != 0; })) {
+      if (watch && std::none_of(ev.begin(), ev.end(), [](int e) { return e != 0; })) {
         // nothing to receive: poll completions -- back to back for a while
         // after the last frame or hand-off, then at the sleep grain
         if (now_ms() - last_progress_ms_ < spin_ms(cfg_)) cpu_relax();
@@ -1237,9 +1241,13 @@ void StreamLoader::launch() {
         continue;
       }
       lk.unlock();
-      // out of output buffers: the consumer is waiting for batches, so
-      // holding assembled ones back for coalescing would only stall it
-      flush_pending(true);
+      // out of output buffers: the consumer is waiting for batches.  With
+      // nothing queued on the GPU, holding assembled ones back would only
+      // stall it; behind queued launches they could not start any sooner, so
+      // they stay until one retires and then leave together
+      // (launch_policy.h).  Every turn reaps and asks again, so a held group
+      // goes the moment room opens.
+      flush_pending(false, true);
       promote_ready();
       lk.lock();
       if (!posted_.empty() || stop_) break;
@@ -1257,6 +1265,15 @@ void StreamLoader::launch() {
         // (blocking: sleep until the oldest completes, then promote it)
         lk.unlock();
         if (blocking_waits()) unready_.front().pending->wait();
+        else std::this_thread::sleep_for(poll_grain());
+        lk.lock();
+        continue;
+      }
+      if (!pending_.empty() && !inflight_.empty()) {
+        // (no host_sync: nothing is unready) batches held behind queued
+        // launches leave when one retires, not when the next buffer is posted
+        lk.unlock();
+        if (blocking_waits()) inflight_.front().copied->wait();
         else std::this_thread::sleep_for(poll_grain());
         lk.lock();
         continue;
@@ -1333,13 +1350,22 @@ hipStream_t StreamLoader::next_decode_stream() {
 // flight over all decode streams.  When the GPU side is the
 // bottleneck the launches therefore grow -- fewer ramp-up/tail phases per
 // image -- and when the producers are, every batch still launches at once.
-void StreamLoader::flush_pending(bool force) {
+// The decision itself is launch_policy.h's; `ending`: nothing more will join
+// the pending batches, `out_of_buffers`: the worker waits for a posted buffer.
+void StreamLoader::flush_pending(bool ending, bool out_of_buffers) {
   if (pending_.empty()) return;
   reap();
-  const bool room = int(inflight_.size()) < cfg_.launch_depth;
-  const bool full = pending_images_ + cfg_.batch_size > kMaxSrcs;
-  const bool copy_waiting = std::any_of(pending_.begin(), pending_.end(), [](const Pending& b) { return !b.direct; });
-  if (!(force || room || full || copy_waiting)) return;
+  policy::State ps;
+  ps.pending_batches = int(pending_.size());
+  ps.pending_images = pending_images_;
+  ps.copy_waiting = std::any_of(pending_.begin(), pending_.end(), [](const Pending& b) { return !b.direct; });
+  ps.inflight = int(inflight_.size());
+  ps.launch_depth = cfg_.launch_depth;
+  ps.batch_size = cfg_.batch_size;
+  ps.max_images = kMaxSrcs;
+  ps.out_of_buffers = out_of_buffers;
+  ps.ending = ending;   // (a stopping loader launches nothing more: stop() hands its pending batches back)
+  if (!policy::flush_now(ps)) return;
   // maximal runs of direct batches go out together; copy-path batches one by one
   std::vector<Pending> group;
   auto emit = [&] {

@@ -51,6 +51,7 @@
 #include "../transport/shmring.h"
 #include "../transport/zmtp.h"
 #include "kernels.h"
+#include "launch_policy.h"
 #include "slot_mirror.h"
 
 namespace btn {
@@ -117,7 +118,9 @@ struct LoaderConfig {
   // loader stream).  Bounded by the runtime's hardware queues.
   int copy_streams = 2;
   // Direct-path launches queued on the loader stream before new batches wait
-  // and coalesce into one launch (0: always hold until 64 images or stream end).
+  // and coalesce into one launch (0: always hold until 64 images or stream
+  // end).  Out of posted buffers the waiting batches still hold while
+  // max(1, launch_depth) launches are queued (launch_policy.h).
   int launch_depth = 2;
   // Direct-path plain-decode launch groups rotate over this many non-blocking
   // HIP streams (1..4; 1: everything on the loader stream).  With 2, launch
@@ -423,7 +426,7 @@ class StreamLoader {
     bool tiled = false;               // every image a key-frame delta: fill + tile scatter
   };
   void launch();
-  void flush_pending(bool force);
+  void flush_pending(bool ending, bool out_of_buffers = false);   // asks launch_policy.h
   void launch_group(std::vector<Pending>& group);
   hipStream_t next_decode_stream();
   void reap(bool wait_all = false);   // release pinned slots of completed H2D copies

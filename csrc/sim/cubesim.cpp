@@ -687,8 +687,14 @@ int main(int argc, char** argv) {
     }
     ++published;
     if (a.fps > 0) {
+      // a stall (no consumer connected yet, a full ring or pipe) is not made
+      // up for by a burst afterwards: the pace resumes from now.  Otherwise
+      // the wait for the first consumer alone left a paced producer a few
+      // hundred frames "behind", i.e. unpaced for as long
       next_due += std::chrono::microseconds(int64_t(1e6 / a.fps));
-      std::this_thread::sleep_until(next_due);
+      const auto now = std::chrono::steady_clock::now();
+      if (next_due < now) next_due = now;
+      else std::this_thread::sleep_until(next_due);
     }
     return true;
   };
