@@ -4,7 +4,7 @@ batches gathered + decoded by one fused kernel per batch.
 
     python benchmarks/bench_replay.py [--frames 4096] [--batch 8] [--steps 2000] [--fill producers|synthetic]
                                       [--crop H W] [--pad P] [--mirror p]
-                                      [--stack K [--stride S] [--nstep N [--gamma G]]]
+                                      [--stack K [--stride S] [--nstep N [--gamma G]] [--prioritized]]
 
 ``--fill producers`` streams the frames from headless Cube producers through
 a raw-u8 DeviceLoader (the record-once, train-many-epochs workflow);
@@ -13,7 +13,8 @@ a raw-u8 DeviceLoader (the record-once, train-many-epochs workflow);
 probability p; ``--pad P``: replicate padding, ``--crop 480 640 --pad 4`` is
 the random shift of DrQ / RAD) inside the same launch.
 ``--stack K`` times frame-stacked transitions, ``--stack K --nstep N`` the
-n-step sample against the 1-step one and against the path composed on top of it.
+n-step sample against the 1-step one and against the path composed on top of it,
+``--stack K --prioritized`` the prioritized sample against the uniform one.
 Prints one JSON line (images/s of decoded fp32 CHW batches); ``effective_tbps``
 counts the bytes read (the window's) plus the bytes written.
 """
@@ -174,6 +175,77 @@ def bench_nstep(a, rb, cfg, fill_s):
                                                              'mirror': cfg.crop.mirror}}), flush=True)
 
 
+def bench_priority(a, rb, cfg, fill_s):
+    """--stack K --prioritized: the prioritized transition sample (priority draw + transition launch) next to
+    the uniform one of this process, the draw alone and one update_priorities call, two rounds each."""
+    import torch
+    from blendtorch import ops
+    dev, B, K, S = rb.device, a.batch, a.stack, a.stride
+    kw = dict(stack=K, stride=S, next_keys=('reward',))
+    if a.nstep:
+        kw.update(nstep=a.nstep, gamma=a.gamma, done_key='done')
+    # priorities over three decades on every slot, as TD errors would leave them
+    g = torch.Generator(device=dev).manual_seed(1)
+    for s in range(0, rb.capacity, 1024):
+        idx = torch.arange(s, min(s + 1024, rb.capacity), device=dev)
+        rb.update_priorities(idx, 10.0 ** (3 * torch.rand(idx.numel(), device=dev, generator=g) - 1.5))
+    beta = torch.full((1,), a.beta, dtype=torch.float32, device=dev)
+
+    def draw_eager():
+        return ops.priority_draw(rb._levels, rb.capacity, rb._max_mass, B, seed=rb.seed, counter=0, beta=beta)
+
+    if a.graph:
+        prio = rb.graphed_transition_sampler(B, cfg, prioritized=True, beta=a.beta, **kw)
+        uniform = rb.graphed_transition_sampler(B, cfg, **kw)
+        draw_eager()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            drawn = draw_eager()
+
+        def draw():
+            graph.replay()
+            return drawn
+    else:
+        prio = lambda: rb.sample_transitions(B, cfg, prioritized=True, beta=beta, **kw)   # noqa: E731
+        uniform = lambda: rb.sample_transitions(B, cfg, **kw)                             # noqa: E731
+        draw = draw_eager
+    up_idx = prio()['index'].clone()
+    up_prio = 10.0 ** (3 * torch.rand(B, device=dev, generator=g) - 1.5)
+
+    def update():
+        return rb.update_priorities(up_idx, up_prio)
+
+    rows = {'prioritized sample': prio, 'uniform sample': uniform, 'priority draw': draw, 'update_priorities': update}
+    times = {k: [] for k in rows}
+    for _ in range(2):
+        for name, fn in rows.items():
+            for _ in range(a.warmup):
+                fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                b = fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / a.steps * 1e6)
+            del b
+    us = {k: min(v) for k, v in times.items()}
+    for name, v in times.items():
+        print(f'{name:20s} {us[name]:10.2f} us/batch   (rounds: {", ".join("%.2f" % t for t in v)})', flush=True)
+    print(f'prioritized - uniform {us["prioritized sample"] - us["uniform sample"]:9.2f} us', flush=True)
+    H, W, C = rb.frame_shape
+    print(json.dumps({'metric': 'prioritized replay transitions us/batch (priority draw + transition launch)',
+                      'value': round(us['prioritized sample'], 2), 'unit': 'us/batch', 'batch': B, 'stack': K,
+                      'stride': S, 'nstep': a.nstep, 'graph': a.graph, 'dtype': a.dtype, 'frame': [H, W, C],
+                      'frames': a.frames, 'tree_levels': len(rb._levels), 'alpha': rb.priority_alpha, 'beta': a.beta,
+                      'us_per_batch': {k: round(v, 2) for k, v in us.items()},
+                      'rounds_us': {k: [round(t, 2) for t in v] for k, v in times.items()},
+                      'prioritized_minus_uniform_us': round(us['prioritized sample'] - us['uniform sample'], 2),
+                      'fill_s': round(fill_s, 2),
+                      'crop': None if cfg.crop is None else {'size': list(cfg.crop.size), 'pad': cfg.crop.pad,
+                                                             'mirror': cfg.crop.mirror}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=4096)
@@ -198,6 +270,11 @@ def main():
                     help='with --stack: time the fused N-step sample, the fused 1-step sample and the N-step '
                          'batch composed on top of the 1-step sample')
     ap.add_argument('--gamma', type=float, default=0.99, help='discount of --nstep')
+    ap.add_argument('--prioritized', action='store_true',
+                    help='with --stack: time the prioritized transition sample next to the uniform one, the '
+                         'priority draw alone and an update_priorities call')
+    ap.add_argument('--alpha', type=float, default=0.6, help='priority exponent of --prioritized')
+    ap.add_argument('--beta', type=float, default=0.4, help='importance-weight exponent of --prioritized')
     ap.add_argument('--frame', type=int, nargs=3, metavar=('H', 'W', 'C'), default=(480, 640, 4),
                     help='frame shape of the synthetic store')
     a = ap.parse_args()
@@ -209,6 +286,8 @@ def main():
         ap.error('--stack needs the synthetic fill and the fused sampler')
     if a.nstep and not a.stack:
         ap.error('--nstep needs --stack')
+    if a.prioritized and not a.stack:
+        ap.error('--prioritized needs --stack')
     if a.fill != 'synthetic' and tuple(a.frame) != (480, 640, 4):
         ap.error('--frame needs the synthetic fill')
 
@@ -216,7 +295,8 @@ def main():
     from blendtorch import btt, ops
     from blendtorch.btt.replay import DeviceReplayBuffer
     dev = torch.device('cuda', 0)
-    rb = DeviceReplayBuffer(a.frames, device=dev)
+    rb = DeviceReplayBuffer(a.frames, device=dev, **(dict(priority_alpha=a.alpha, priority_stride=a.stride)
+                                                     if a.prioritized else {}))
     t0 = time.perf_counter()
     if a.fill == 'synthetic':
         g = torch.Generator(device=dev).manual_seed(0)
@@ -241,6 +321,8 @@ def main():
     fill_s = time.perf_counter() - t0
     crop = None if a.crop is None else ops.Crop(tuple(a.crop), mirror=a.mirror, pad=a.pad)
     cfg = ops.DecodeConfig.unit(channels='rgb', gamma=2.2, dtype=a.dtype, crop=crop)
+    if a.prioritized:
+        return bench_priority(a, rb, cfg, fill_s)
     if a.nstep:
         return bench_nstep(a, rb, cfg, fill_s)
     if a.stack:

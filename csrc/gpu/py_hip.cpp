@@ -21,6 +21,7 @@
 #include "comm.h"
 #include "kernels.h"
 #include "loader.h"
+#include "priority.h"
 
 namespace py = pybind11;
 using namespace btn;
@@ -63,6 +64,21 @@ hipStream_t stream_of(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 void check(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// PriorityTree from Python; a malformed one (too many levels, mismatched lists) has nlevels = 0: the launchers refuse it
+PriorityTree priority_tree_from(const std::vector<uintptr_t>& levels, const std::vector<int64_t>& counts,
+                                int64_t capacity, uintptr_t max_mass) {
+  PriorityTree t;
+  t.capacity = capacity;
+  t.max_mass = ptr<uint32_t>(max_mass);
+  if (levels.size() != counts.size() || levels.size() > size_t(kMaxPriorityLevels)) return t;
+  t.nlevels = int(levels.size());
+  for (int l = 0; l < t.nlevels; ++l) {
+    t.level[l] = ptr<void>(levels[size_t(l)]);
+    t.count[l] = counts[size_t(l)];
+  }
+  return t;
 }
 
 // Native default_collate of a batch's metadata: for every key of the first
@@ -580,6 +596,48 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("nstep") = 0, py::arg("gamma") = 1.0, py::arg("reward") = uintptr_t(0), py::arg("done") = uintptr_t(0),
         py::arg("return_out") = uintptr_t(0), py::arg("discount_out") = uintptr_t(0),
         py::arg("steps_out") = uintptr_t(0));
+
+  // prioritized replay (priority.h): the tree is (levels, counts, capacity, max_mass), device pointers
+  m.def("priority_draw",
+        [](std::vector<uintptr_t> levels, std::vector<int64_t> counts, int64_t capacity, uintptr_t max_mass, int B,
+           uint64_t seed, uintptr_t counter, uint64_t ctr_value, int advance, uintptr_t beta, uintptr_t ticket,
+           uintptr_t index_out, uintptr_t mass_out, uintptr_t prob_out, uintptr_t weight_out, uintptr_t stream) {
+          PriorityDrawParams d;
+          d.B = B;
+          d.seed = seed;
+          d.counter = ptr<uint64_t>(counter);
+          d.ctr_value = ctr_value;
+          d.advance = advance;
+          d.beta = ptr<const float>(beta);
+          d.ticket = ptr<uint32_t>(ticket);
+          d.index_out = ptr<int64_t>(index_out);
+          d.mass_out = ptr<uint32_t>(mass_out);
+          d.prob_out = ptr<float>(prob_out);
+          d.weight_out = ptr<float>(weight_out);
+          check(priority_draw(priority_tree_from(levels, counts, capacity, max_mass), d, stream_of(stream)),
+                "priority_draw");
+        },
+        py::arg("levels"), py::arg("counts"), py::arg("capacity"), py::arg("max_mass"), py::arg("B"), py::arg("seed"),
+        py::arg("counter"), py::arg("ctr_value"), py::arg("advance"), py::arg("beta"), py::arg("ticket"),
+        py::arg("index_out"), py::arg("mass_out"), py::arg("prob_out"), py::arg("weight_out"), py::arg("stream"));
+  m.def("priority_update",
+        [](std::vector<uintptr_t> levels, std::vector<int64_t> counts, int64_t capacity, uintptr_t max_mass,
+           uintptr_t index, uintptr_t priority, int B, double alpha, uintptr_t stream) {
+          check(priority_update(priority_tree_from(levels, counts, capacity, max_mass), ptr<const int64_t>(index),
+                                ptr<const float>(priority), B, float(alpha), stream_of(stream)),
+                "priority_update");
+        },
+        py::arg("levels"), py::arg("counts"), py::arg("capacity"), py::arg("max_mass"), py::arg("index"),
+        py::arg("priority"), py::arg("B"), py::arg("alpha"), py::arg("stream"));
+  m.def("priority_extend",
+        [](std::vector<uintptr_t> levels, std::vector<int64_t> counts, int64_t capacity, uintptr_t max_mass,
+           int64_t start, int64_t n, int64_t head, int64_t size, int64_t stride, uintptr_t first, uintptr_t stream) {
+          check(priority_extend(priority_tree_from(levels, counts, capacity, max_mass), start, n, head, size, stride,
+                                ptr<const uint8_t>(first), stream_of(stream)),
+                "priority_extend");
+        },
+        py::arg("levels"), py::arg("counts"), py::arg("capacity"), py::arg("max_mass"), py::arg("start"), py::arg("n"),
+        py::arg("head"), py::arg("size"), py::arg("stride"), py::arg("first"), py::arg("stream"));
 
   m.def("multi_cast",
         [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst, std::vector<int64_t> numel, int mode,

@@ -31,6 +31,11 @@ epoch after the first then runs at HBM speed without touching the host:
   starts come from a one-byte ``first`` metadata column.  ``nstep=n,
   gamma=g`` adds the n-step return, its bootstrap discount and the stack n
   steps later, in the same launch.
+* ``DeviceReplayBuffer(..., priority_alpha=a)`` + ``sample_transitions(...,
+  prioritized=True)``: prioritized experience replay.  The priorities are
+  integer masses in a 64-ary sum tree in HBM; a small launch in front of the
+  transition launch draws the anchors by tree descent (stratified) and the
+  importance weights, ``update_priorities`` writes TD errors back.
 
 On a CPU device the same API runs with the fp32 reference ops (tests, hosts
 without a GPU). On a GPU device the HIP kernels are required and fail loudly
@@ -69,9 +74,20 @@ class DeviceReplayBuffer:
         Where frames live (``'cuda:N'`` for HBM, ``'cpu'`` for the reference path).
     image_key: str
         Message key of the image when filling from recordings / loaders.
+    priority_alpha: float, optional
+        Keep a priority per stored transition (prioritized experience replay,
+        Schaul et al. 2016): ``sample_transitions(prioritized=True)`` draws in
+        proportion to ``priority ** priority_alpha`` and
+        ``update_priorities`` writes TD errors back.  ``None``: nothing is
+        allocated and nothing changes.
+    first_key, priority_stride:
+        The episode-start column and the frames per environment step of the
+        transitions the priorities are kept for (``sample_transitions``'s
+        ``first_key`` and ``stride``); ``extend`` needs that column then.
     """
 
-    def __init__(self, capacity: int, device=None, image_key: str = 'image', seed: Optional[int] = None):
+    def __init__(self, capacity: int, device=None, image_key: str = 'image', seed: Optional[int] = None,
+                 priority_alpha: Optional[float] = None, first_key: str = 'first', priority_stride: int = 1):
         if capacity < 1:
             raise ValueError('capacity must be >= 1')
         self.capacity = int(capacity)
@@ -90,6 +106,19 @@ class DeviceReplayBuffer:
         self._state: Optional[torch.Tensor] = None
         if self.device.type == 'cuda':
             ops.hip_ext()   # fail loudly here, not at the first sample()
+        # prioritized replay (None: nothing is allocated): the mass tree of ops.priority_tree over the slots,
+        # kept eligible-or-zero by extend() for transitions of `priority_stride` with episode starts `first_key`
+        self.priority_alpha = None if priority_alpha is None else float(priority_alpha)
+        self.first_key, self.priority_stride = first_key, int(priority_stride)
+        self._levels = self._max_mass = self._beta = None
+        if self.priority_alpha is not None:
+            if not 0.0 <= self.priority_alpha <= 16.0:
+                raise ValueError('priority_alpha must lie in [0, 16]')
+            if not 1 <= self.priority_stride < self.capacity:
+                raise ValueError('priority_stride must lie in [1, capacity)')
+            self._levels = ops.priority_tree(np.zeros(self.capacity, np.uint32), device=self.device)
+            self._max_mass = torch.from_numpy(np.array([ops.PRIORITY_ONE], np.uint32)).to(self.device)
+            self._beta = [None, torch.zeros(1, dtype=torch.float32, device=self.device)]   # host value, device scalar
 
     # -- filling ---------------------------------------------------------------
     def __len__(self):
@@ -129,7 +158,9 @@ class DeviceReplayBuffer:
             imgs = imgs[n - self.capacity:]
             meta = {k: v[n - self.capacity:] for k, v in meta.items()}
             n = self.capacity
-        pos = 0
+        if self._levels is not None:
+            self._first_column()
+        pos, start = 0, self._next
         while pos < n:
             k = min(n - pos, self.capacity - self._next)
             self.store[self._next:self._next + k].copy_(imgs[pos:pos + k], non_blocking=True)
@@ -138,9 +169,73 @@ class DeviceReplayBuffer:
             self._next = (self._next + k) % self.capacity
             pos += k
         self._size = min(self.capacity, self._size + n)
+        if self._levels is not None and n:   # the appended slots and the steps before them change eligibility
+            args = (self.capacity, start, n, self._next, self._size, self.priority_stride)
+            if self.device.type == 'cuda':
+                ops.priority_extend(self._levels, self.capacity, self._max_mass, *args[1:], self._first_column())
+            else:
+                ops.reference_priority_extend([lev.numpy() for lev in self._levels], int(self._max_mass.numpy()[0]),
+                                              *args, self._first_column().numpy())
         if self._state is not None:   # a graphed transition sampler reads the ring state from the device
             self._state.copy_(torch.tensor([self._next, self._size], dtype=torch.int64))
         return self
+
+    # -- priorities ------------------------------------------------------------
+    def _first_column(self):
+        first = self.meta.get(self.first_key)
+        if first is None or first.dim() != 1 or first.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f'a prioritized buffer needs a uint8 / bool [capacity] metadata column {self.first_key!r} '
+                             '(episode starts): extend(frames, ..., %s=flags)' % self.first_key)
+        return first
+
+    def _need_priorities(self):
+        if self._levels is None:
+            raise ValueError('this buffer keeps no priorities: DeviceReplayBuffer(..., priority_alpha=...)')
+
+    @property
+    def priority_mass(self) -> torch.Tensor:
+        """uint32 [capacity], read-only: the mass of the transition anchored at
+        each slot (``ops.reference_priority_mass``; 0: may not be drawn)."""
+        self._need_priorities()
+        return self._levels[0][:self.capacity].clone()
+
+    def update_priorities(self, index, priority):
+        """Write priorities (TD errors; float32) back for the anchors ``index``
+        of a batch: slot ``index[b]`` takes mass ``clamp(rint(priority[b] **
+        priority_alpha * 65536), 1, 2**32 - 1)``.  Of duplicate anchors the
+        last entry wins; an anchor that may not be drawn stays excluded.  On a
+        GPU one launch per 1024 entries, no host sync."""
+        self._need_priorities()
+        index = _as_tensor(index, self.device).to(torch.int64).reshape(-1)
+        priority = _as_tensor(priority, self.device).to(torch.float32).reshape(-1)
+        if index.numel() != priority.numel():
+            raise ValueError('update_priorities: one priority per index')
+        for s in range(0, int(index.numel()), ops.MAX_PRIORITY_B):
+            i, p = index[s:s + ops.MAX_PRIORITY_B], priority[s:s + ops.MAX_PRIORITY_B]
+            if self.device.type == 'cuda':
+                ops.priority_update(self._levels, self.capacity, self._max_mass, i, p, self.priority_alpha)
+            else:
+                mx = ops.reference_priority_update([lev.numpy() for lev in self._levels], int(self._max_mass.numpy()[0]),
+                                                   i.numpy(), p.numpy(), self.priority_alpha)
+                self._max_mass.numpy()[0] = mx
+        return self
+
+    def _priority_draw(self, B, ctr, beta, advance):
+        """(index, prob, weight) of a prioritized batch at Philox counter ``ctr``; beta: a value or a device scalar."""
+        if isinstance(beta, torch.Tensor):
+            beta_t = beta
+        else:
+            if self._beta[0] != float(beta):      # the device scalar follows the host value
+                self._beta[0] = float(beta)
+                self._beta[1].fill_(float(beta))
+            beta_t = self._beta[1]
+        if self.device.type == 'cuda':
+            idx, _, prob, weight = ops.priority_draw(self._levels, self.capacity, self._max_mass, B, seed=self.seed,
+                                                     counter=ctr, beta=beta_t, advance=advance)
+            return idx, prob, weight
+        idx, mass, prob = ops.reference_priority_draw([lev.numpy() for lev in self._levels], self.seed, int(ctr), B)
+        weight = ops.reference_priority_weights(mass, float(beta_t[0])).astype(np.float32)
+        return torch.from_numpy(idx), torch.from_numpy(prob), torch.from_numpy(weight)
 
     def fill_from(self, batches, max_items: int):
         """Append frames from an iterable of batch dicts (e.g. a
@@ -392,9 +487,16 @@ class DeviceReplayBuffer:
 
     # -- frame-stacked transitions ------------------------------------------------
     def _transitions(self, B, idx, decode, stack, stride, first_key, next_keys, shared_window, _counter,
-                     nstep=None, gamma=0.99, reward_key='reward', done_key=None):
+                     nstep=None, gamma=0.99, reward_key='reward', done_key=None, prioritized=False, beta=0.4):
         if self._size == 0:
             raise IndexError('empty replay buffer')
+        if prioritized:
+            self._need_priorities()
+            if int(stride) != self.priority_stride or first_key != self.first_key:
+                raise ValueError(f'the priorities are kept for stride = {self.priority_stride} and first_key = '
+                                 f'{self.first_key!r} (the constructor\'s)')
+            if not 1 <= B <= ops.MAX_PRIORITY_B:
+                raise ValueError(f'a prioritized batch holds 1 .. {ops.MAX_PRIORITY_B} transitions')
         ops._transition_cfg(decode, 'DeviceReplayBuffer transitions')
         first = self.meta.get(first_key)
         if first is None or first.dim() != 1 or first.dtype not in (torch.uint8, torch.bool):
@@ -430,6 +532,13 @@ class DeviceReplayBuffer:
             ctr = self._ctr
             if idx is None or (crop is not None and crop.kind == 'random'):   # something is drawn
                 self._ctr += B
+        prio = None
+        if prioritized:
+            # the anchors come from the priority tree, drawn in front of the transition launch at the same
+            # counter; that launch then takes them as given ones.  A device counter moves on by B once: behind
+            # the transition launch if it draws windows, else in the draw.
+            windows_drawn = crop is not None and crop.kind == 'random'
+            idx, *prio = self._priority_draw(B, ctr, beta, advance=isinstance(ctr, torch.Tensor) and not windows_drawn)
         if self.device.type == 'cuda':
             if not self.store.is_contiguous():
                 raise ValueError('transitions need a contiguous store')
@@ -445,6 +554,8 @@ class DeviceReplayBuffer:
                 batch.update(crop=info['crop'], next_crop=info['next_crop'])
             if nstep is not None:
                 batch.update({k: info[k] for k in ('nstep_return', 'nstep_discount', 'nstep_steps')})
+            if prio is not None:
+                batch.update(prob=prio[0], weight=prio[1])
             return batch
         # the reference path: the numpy references of the kernel's draws + reference_decode
         ring = (self._next, self._size, self.capacity, stride, stack, first.numpy())
@@ -477,11 +588,14 @@ class DeviceReplayBuffer:
                                                         done=nkw['done'])
             batch.update(nstep_return=torch.from_numpy(ret), nstep_discount=torch.from_numpy(disc),
                          nstep_steps=torch.from_numpy(steps))
+        if prio is not None:
+            batch.update(prob=prio[0], weight=prio[1])
         return batch
 
     def sample_transitions(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                            stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
-                           _counter=None, nstep=None, gamma: float = 0.99, reward_key: str = 'reward', done_key=None):
+                           _counter=None, nstep=None, gamma: float = 0.99, reward_key: str = 'reward', done_key=None,
+                           prioritized: bool = False, beta=0.4):
         """A batch of frame-stacked transitions out of the frame-once store.
 
         Storage convention (nothing about ``extend`` changes): an RL loop
@@ -531,9 +645,22 @@ class DeviceReplayBuffer:
         mask.  Without one the walk merely truncates at the episode's end
         (time-limit semantics: the last observation still bootstraps).
         ``index`` and ``valid`` are the 1-step ones whatever ``nstep`` is;
-        ``ops.nstep_transitions`` is the reference."""
+        ``ops.nstep_transitions`` is the reference.
+
+        ``prioritized`` (a buffer built with ``priority_alpha``): the anchors
+        are drawn in proportion to their priority instead -- stratified, one
+        per ``batch_size``-th of the total mass, by a small launch in front
+        of the transition launch (``ops.priority_draw``), which then takes
+        them as given anchors at the same counter: windows, stacks and n-step
+        returns are what :meth:`gather_transitions` gives for them.  The
+        batch gains ``prob`` (float32: mass / total mass) and ``weight``
+        (float32: the importance-sampling weight ``(N prob)^-beta`` divided
+        by the batch maximum).  New transitions enter with the largest
+        priority written so far; :meth:`update_priorities` writes TD errors
+        back.  ``valid`` is all True unless no stored transition is eligible.
+        The Philox counter advances by ``batch_size`` per sample."""
         return self._transitions(int(batch_size), None, decode, stack, stride, first_key, next_keys, shared_window,
-                                 _counter, nstep, gamma, reward_key, done_key)
+                                 _counter, nstep, gamma, reward_key, done_key, prioritized=bool(prioritized), beta=beta)
 
     def gather_transitions(self, idx: torch.Tensor, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                            stride: int = 1, first_key: str = 'first', next_keys=(), shared_window: bool = False,
@@ -549,18 +676,28 @@ class DeviceReplayBuffer:
     def graphed_transition_sampler(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), stack: int = 1,
                                    stride: int = 1, first_key: str = 'first', next_keys=(),
                                    shared_window: bool = False, warmup: int = 3, nstep=None, gamma: float = 0.99,
-                                   reward_key: str = 'reward', done_key=None):
+                                   reward_key: str = 'reward', done_key=None, prioritized: bool = False, beta=0.4):
         """:meth:`sample_transitions` captured once as a HIP graph.  The
         Philox counter lives in device memory (as in :meth:`graphed_sampler`)
         and so does the ring state: the kernel reads ``(head, size)`` from a
         device tensor that ``extend`` refreshes once such a sampler exists, so
         ONE capture serves a buffer that grows every environment step.  The
         returned callable replays the graph and returns the same static
-        output dict every time."""
+        output dict every time.  ``prioritized``: both launches are captured;
+        the callable's ``.beta`` is the device float32 scalar the draw reads
+        (``sampler.beta.fill_(b)`` anneals it between replays)."""
         kw = dict(stack=stack, stride=stride, first_key=first_key, next_keys=next_keys, shared_window=shared_window,
                   nstep=nstep, gamma=gamma, reward_key=reward_key, done_key=done_key)
+        beta_t = None
+        if prioritized:
+            self._need_priorities()
+            beta_t = torch.full((1,), float(beta), dtype=torch.float32, device=self.device)
+            kw.update(prioritized=True, beta=beta_t)
         if self.device.type != 'cuda':
-            return lambda: self.sample_transitions(batch_size, decode, **kw)
+            def sample():
+                return self.sample_transitions(batch_size, decode, **kw)
+            sample.beta = beta_t
+            return sample
         if self._state is None:
             self._state = torch.tensor([self._next, self._size], dtype=torch.int64, device=self.device)
         counter = torch.tensor([self._ctr], dtype=torch.int64, device=self.device)
@@ -580,6 +717,7 @@ class DeviceReplayBuffer:
             return out
         replay.graph = graph
         replay.counter = counter
+        replay.beta = beta_t
         return replay
 
     def batches(self, batch_size: int, decode: DecodeConfig = DecodeConfig(), shuffle: bool = True,

@@ -31,6 +31,8 @@ import numpy as np
 __all__ = [
     'DecodeConfig', 'ColorJitter', 'Crop', 'crop_windows', 'crop_points', 'ResizedCrop', 'resized_windows', 'resized_crop_points', 'philox_windows', 'replay_windows', 'color_jitter_matrix', 'jitter_factors', 'hip_ext', 'hip_available', 'gamma_lut', 'build_lut', 'build_table', 'decode', 'decode_gather',
     'color4x4', 'replay_transitions', 'philox_transitions', 'given_transitions', 'transition_windows',
+    'priority_tree', 'priority_draw', 'priority_update', 'priority_extend', 'reference_priority_draw',
+    'reference_priority_mass', 'reference_priority_weights', 'reference_priority_update', 'reference_priority_extend',
     'project', 'adaptive_avg_pool_nhwc', 'AdaptiveAvgPool2d', 'batch_norm_leaky_relu', 'BatchNormLeakyReLU2d',
     'reference_decode', 'reference_color4x4', 'reference_project', 'reference_gamma',
 ]
@@ -1683,6 +1685,254 @@ def replay_transitions(store, head: int, size: int, batch: int, cfg: DecodeConfi
                            src, dst, nbytes, nsrc, ndst, nnbytes, _stream(dev), table_only(cfg, dev), **ckw, **nkw)
     info.update(index=idx_out, next_index=nidx_out, valid=valid)
     return out, info
+
+
+# ---- prioritized replay -----------------------------------------------------------------------------------------
+# csrc/gpu/priority.h has the contract.  A transition anchored at slot s carries a uint32 mass: 0 = may not be
+# drawn, else clamp(rint(priority^alpha * 65536), 1, 2^32 - 1).  The masses are level 0 of a 64-ary sum tree
+# (uint64 sums above), so a draw in proportion to mass is a descent of ceil(log64(capacity)) rounds -- and every
+# number in it is an integer: the numpy references below reproduce the kernels bit for bit.
+
+PRIORITY_ONE = 65536              # the mass of priority 1
+PRIORITY_TOP = 2 ** 32 - 1
+PRIORITY_BLOCK = 6                # Philox counter word 3 of the prioritized draw (0 .. 5: replay_transitions)
+MAX_PRIORITY_B = 1024
+MAX_PRIORITY_LEVELS = 6
+
+
+def priority_level_counts(capacity: int):
+    """Allocated nodes per level of the tree over ``capacity`` slots: level 0
+    is ``capacity`` rounded up to a multiple of 64; every further level has a
+    64th of the one below, rounded up to a multiple of 64 while a level above
+    it exists; the top level has at most 64 nodes."""
+    capacity = int(capacity)
+    if not 1 <= capacity <= 2 ** 31:
+        raise ValueError('capacity must lie in [1, 2**31]')
+    counts = [(capacity + 63) // 64 * 64]
+    while counts[-1] > 64:
+        c = counts[-1] // 64
+        counts.append((c + 63) // 64 * 64 if c > 64 else c)
+    return counts
+
+
+def priority_tree(masses, device=None):
+    """The levels of the sum tree over the uint32 ``masses`` [capacity]:
+    ``[uint32 [count0], uint64 [count1], ...]`` (:func:`priority_level_counts`),
+    padding 0.  numpy arrays, or with ``device`` torch tensors there."""
+    if hasattr(masses, 'detach'):
+        masses = masses.detach().cpu().numpy()
+    m = np.asarray(masses)
+    if m.ndim != 1 or m.dtype.kind not in 'iu' or (m.size and (int(m.min()) < 0 or int(m.max()) > PRIORITY_TOP)):
+        raise ValueError('masses must be a 1-d array of integers in [0, 2**32)')
+    counts = priority_level_counts(m.shape[0])
+    levels = [np.zeros(counts[0], np.uint32)]
+    levels[0][:m.shape[0]] = m
+    for c in counts[1:]:
+        below = levels[-1].astype(np.uint64).reshape(-1, 64).sum(axis=1, dtype=np.uint64)
+        lev = np.zeros(c, np.uint64)
+        lev[:below.shape[0]] = below
+        levels.append(lev)
+    if device is None:
+        return levels
+    import torch
+    return [torch.from_numpy(lev).to(device) for lev in levels]
+
+
+def reference_priority_mass(priority, alpha: float = 1.0) -> np.ndarray:
+    """uint32 masses of float32 ``priority``: ``clamp(rint(p^alpha * 65536), 1,
+    2^32 - 1)`` with negative and NaN priorities counted as 0.  ``alpha == 1``
+    is computed in float32 as the kernel does (a scaling by 2^16: exact);
+    any other alpha in float64 (the kernel's ``powf`` is within 16 ulp)."""
+    p = np.asarray(priority, np.float32)
+    with np.errstate(all='ignore'):
+        p = np.where(p > 0, p, np.float32(0))
+        x = p * np.float32(PRIORITY_ONE) if float(alpha) == 1.0 else p.astype(np.float64) ** float(alpha) * PRIORITY_ONE
+        m = np.clip(np.rint(x.astype(np.float64)), 1, PRIORITY_TOP)
+    return m.astype(np.uint32)
+
+
+def _priority_levels(levels):
+    levels = list(levels)
+    counts = priority_level_counts(levels[0].shape[0])
+    if [int(lev.shape[0]) for lev in levels] != counts or levels[0].dtype != np.uint32 \
+            or any(lev.dtype != np.uint64 for lev in levels[1:]):
+        raise ValueError('levels are not a priority tree (priority_tree builds one)')
+    return levels
+
+
+def reference_priority_draw(levels, seed: int, counter: int, B: int):
+    """The stratified draw of the ``priority_draw`` kernel (numpy reference):
+    ``(index int64 [B], mass uint32 [B], prob float32 [B])``.  With T the total
+    mass, image b draws ``u = lo + ((r64 * (hi - lo)) >> 64)`` in its stratum
+    ``lo = b T // B``, ``hi = (b + 1) T // B``, ``r64 = (o0 << 32) | o1`` from
+    the Philox block with key ``seed`` and counter words ``(b, counter,
+    counter >> 32, 6)``, and descends: per level the first child whose
+    inclusive prefix sum exceeds ``u`` is taken and ``u`` drops by its
+    exclusive prefix.  ``prob = float32(mass) / float32(T)``.  ``T == 0``
+    gives zeros."""
+    levels = _priority_levels(levels)
+    B = int(B)
+    index, mass, prob = np.zeros(B, np.int64), np.zeros(B, np.uint32), np.zeros(B, np.float32)
+    T = sum(int(v) for v in levels[-1])
+    if T == 0 or B == 0:
+        return index, mass, prob
+    o0, o1, _, _ = _philox_blocks(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), B, PRIORITY_BLOCK)
+    u = np.zeros(B, np.uint64)
+    for b in range(B):
+        lo, hi = b * T // B, (b + 1) * T // B
+        u[b] = lo + ((((int(o0[b]) << 32) | int(o1[b])) * (hi - lo)) >> 64)
+    node = np.zeros(B, np.int64)
+    lane = np.arange(64, dtype=np.int64)
+    for lev in reversed(levels):
+        i = node[:, None] * 64 + lane
+        v = np.where(i < lev.shape[0], lev[np.minimum(i, lev.shape[0] - 1)].astype(np.uint64), np.uint64(0))
+        pre = np.cumsum(v, axis=1, dtype=np.uint64)
+        over = pre > u[:, None]
+        assert over.any(axis=1).all(), 'inconsistent priority tree'
+        pick = np.argmax(over, axis=1)
+        rows = np.arange(B)
+        u = u - (pre[rows, pick] - v[rows, pick])
+        node = node * 64 + pick
+        last = v[rows, pick]
+    index[:] = node
+    mass[:] = last.astype(np.uint32)
+    prob[:] = mass.astype(np.float32) / np.array([T], np.uint64).astype(np.float32)[0]
+    return index, mass, prob
+
+
+def reference_priority_weights(mass, beta: float) -> np.ndarray:
+    """float64 importance-sampling weights of one batch: ``(N prob)^-beta``
+    normalised by the batch maximum = ``(min mass / mass)^beta``; zeros for a
+    batch without mass (``T == 0``)."""
+    m = np.asarray(mass).astype(np.float64)
+    if m.size == 0 or m.min() <= 0:
+        return np.zeros(m.shape, np.float64)
+    return (m.min() / m) ** float(beta)
+
+
+def _priority_set(levels, slot, new):
+    """leaf ``slot`` takes mass ``new``; the difference goes up the tree (Python ints: exact)."""
+    delta = int(new) - int(levels[0][slot])
+    levels[0][slot] = new
+    node = slot
+    for lev in levels[1:]:
+        node >>= 6
+        lev[node] = np.uint64(int(lev[node]) + delta)
+
+
+def reference_priority_update(levels, max_mass: int, index, priority, alpha: float = 1.0) -> int:
+    """``priority_update`` on numpy ``levels``, in place; returns the new
+    ``max_mass``.  Of duplicate indices the highest batch position wins, a
+    slot of mass 0 stays 0, an index outside the store is ignored."""
+    levels = _priority_levels(levels)
+    index = np.asarray(index, np.int64).reshape(-1)
+    new = reference_priority_mass(np.asarray(priority, np.float32).reshape(-1), alpha)
+    winner = {int(s): b for b, s in enumerate(index)}
+    for s, b in winner.items():
+        if 0 <= s < levels[0].shape[0] and levels[0][s] != 0:
+            _priority_set(levels, s, int(new[b]))
+            max_mass = max(int(max_mass), int(new[b]))
+    return int(max_mass)
+
+
+def reference_priority_extend(levels, max_mass: int, capacity: int, start: int, n: int, head: int, size: int,
+                              stride: int, first):
+    """``priority_extend`` on numpy ``levels``, in place: after an append of
+    ``n`` frames at slots ``start ..`` (mod ``capacity``; ``head`` / ``size``
+    the ring state after it) every appended slot x and every ``x - stride``
+    takes ``max_mass`` if x is stored, ``age(x) >= stride`` and
+    ``first[(x + stride) % capacity] == 0``, else 0."""
+    levels = _priority_levels(levels)
+    first = np.asarray(first).reshape(-1) != 0
+    for i in range(2 * int(n)):
+        x = (start + i if i < n else start + (i - n) - stride) % capacity
+        age = (head - 1 - x) % capacity
+        ok = age < size and age >= stride and not first[(x + stride) % capacity]
+        _priority_set(levels, x, int(max_mass) if ok else 0)
+
+
+_PRIORITY_TICKETS = {}
+
+
+def _priority_args(levels, capacity, max_mass):
+    import torch
+    dev = levels[0].device
+    counts = priority_level_counts(capacity)
+    if [int(lev.shape[0]) for lev in levels] != counts or levels[0].dtype != torch.uint32 \
+            or any(lev.dtype != torch.uint64 or lev.device != dev for lev in levels[1:]) or not levels[0].is_cuda:
+        raise ValueError('levels are not a priority tree on one GPU (priority_tree(masses, device) builds one)')
+    if max_mass.dtype != torch.uint32 or max_mass.numel() != 1 or max_mass.device != dev:
+        raise ValueError('max_mass must be a uint32 [1] tensor on the tree\'s device')
+    return dict(levels=[lev.data_ptr() for lev in levels], counts=counts, capacity=int(capacity),
+                max_mass=max_mass.data_ptr()), dev
+
+
+def priority_draw(levels, capacity: int, max_mass, batch: int, seed: int = 0, counter=0, beta=None, advance=False):
+    """Stratified draw of ``batch`` slots in proportion to their mass, ONE small
+    launch of the gfx950 kernel (one wave per item; :func:`reference_priority_draw`
+    has the contract): ``(index int64, mass uint32, prob float32, weight float32)``,
+    each [batch].  ``levels`` / ``max_mass``: the device tree of
+    :func:`priority_tree`.  ``counter``: an int, or a device int64 [1] tensor
+    read by the kernel; ``advance`` then adds ``batch`` to it in the same
+    launch (for a caller whose next launch does not).  ``beta``: a device
+    float32 [1] tensor, read by the kernel -- a captured graph follows an
+    annealed beta.  ``weight = (min mass of the batch / mass)^beta``."""
+    import torch
+    ext = hip_ext()
+    tree, dev = _priority_args(levels, capacity, max_mass)
+    batch = int(batch)
+    if not 1 <= batch <= MAX_PRIORITY_B:
+        raise ValueError(f'batch must lie in [1, {MAX_PRIORITY_B}]')
+    if not isinstance(beta, torch.Tensor) or beta.dtype != torch.float32 or beta.numel() != 1 or beta.device != dev:
+        raise ValueError('beta must be a float32 [1] tensor on the tree\'s device')
+    ctr_ptr, ctr_value = 0, 0
+    if isinstance(counter, torch.Tensor):
+        if counter.dtype != torch.int64 or counter.numel() < 1 or counter.device != dev:
+            raise ValueError('a device counter must be an int64 tensor on the tree\'s device')
+        ctr_ptr = counter.data_ptr()
+    else:
+        ctr_value = int(counter) & (2 ** 64 - 1)
+    ticket = _PRIORITY_TICKETS.get(dev)
+    if ticket is None:
+        ticket = _PRIORITY_TICKETS[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    index = torch.empty(batch, dtype=torch.int64, device=dev)
+    mass = torch.empty(batch, dtype=torch.uint32, device=dev)
+    prob = torch.empty(batch, dtype=torch.float32, device=dev)
+    weight = torch.empty(batch, dtype=torch.float32, device=dev)
+    ext.priority_draw(**tree, B=batch, seed=int(seed) & (2 ** 64 - 1), counter=ctr_ptr, ctr_value=ctr_value,
+                      advance=int(bool(advance)), beta=beta.data_ptr(), ticket=ticket.data_ptr(),
+                      index_out=index.data_ptr(), mass_out=mass.data_ptr(), prob_out=prob.data_ptr(),
+                      weight_out=weight.data_ptr(), stream=_stream(dev))
+    return index, mass, prob, weight
+
+
+def priority_update(levels, capacity: int, max_mass, index, priority, alpha: float = 1.0):
+    """Write priorities back: slot ``index[b]`` takes the mass of
+    ``priority[b]`` (:func:`reference_priority_update`), one launch of one
+    block, at most 1024 entries."""
+    import torch
+    ext = hip_ext()
+    tree, dev = _priority_args(levels, capacity, max_mass)
+    index = index.to(dev, torch.int64).reshape(-1).contiguous()
+    priority = priority.to(dev, torch.float32).reshape(-1).contiguous()
+    if index.numel() != priority.numel() or index.numel() > MAX_PRIORITY_B:
+        raise ValueError(f'index and priority need the same length, at most {MAX_PRIORITY_B}')
+    if not 0.0 <= float(alpha) <= 16.0:
+        raise ValueError('alpha must lie in [0, 16]')
+    ext.priority_update(**tree, index=index.data_ptr(), priority=priority.data_ptr(), B=int(index.numel()),
+                        alpha=float(alpha), stream=_stream(dev))
+
+
+def priority_extend(levels, capacity: int, max_mass, start: int, n: int, head: int, size: int, stride: int, first):
+    """The eligibility refresh behind an append (:func:`reference_priority_extend`), one launch."""
+    import torch
+    ext = hip_ext()
+    tree, dev = _priority_args(levels, capacity, max_mass)
+    if first.device != dev or first.dtype not in (torch.uint8, torch.bool) or tuple(first.shape) != (int(capacity),) \
+            or not first.is_contiguous():
+        raise ValueError(f'first must be a contiguous uint8 / bool [{capacity}] tensor on {dev}')
+    ext.priority_extend(**tree, start=int(start), n=int(n), head=int(head), size=int(size), stride=int(stride),
+                        first=first.data_ptr(), stream=_stream(dev))
 
 
 def color4x4(images, M=None, bias=(0.0, 0.0, 0.0, 0.0), gamma=None, flip=False, cout=4, jitter=None, pivot=127.5):
