@@ -1664,12 +1664,17 @@ void StreamLoader::launch_group(std::vector<Pending>& group) {
     // that launch takes from the copy was written by earlier, whole reads.
     // reap() / promote_ready() invalidate the slot's entry all the same, so
     // nothing later relies on a copy a torn read produced.
-    // With block masks the same holds block by block: a producer that takes a
-    // slot back first restores what the slot's last frame drew -- pixels of
-    // this frame's spans, which the next frame's mask contains because it is
-    // the union of both frames' blocks -- and then draws the next frame, whose
-    // spans are in that mask too.  It writes nowhere else, so torn bytes lie
-    // inside the next frame's set blocks and are read again from the host.
+    // With block masks the same holds block by block, by the rule a producer's
+    // mask obeys: every byte the render of a frame stores lies in a set block
+    // of that frame's mask, stores that a later one of the same render
+    // overwrites included, and every byte outside the set blocks is what the
+    // slot held one generation earlier (the render reports the blocks it
+    // stored into, sim::Renderer::render's `written`; it leaves alone, and
+    // does not report, shadow pixels the slot's last frame left as shadow).
+    // A producer that takes a slot back writes nothing before that render,
+    // so torn bytes lie inside the next frame's set blocks and are read
+    // again from the host; a block clear in that mask was not stored into
+    // while this launch read it.
     //
     // Frames that admit a block grid (W % 64 == 0, W <= 1024) take
     // decode_delta_blocks whether their producer sent a mask or only a

@@ -28,7 +28,11 @@
 // --bench N (no sockets: render N frames into 8 rotating buffers, full vs
 // incremental (DirtyRect) rendering, and report the byte mismatches -- 0;
 // with --shm-layout planar the incremental frames are rgb_a slots, compared
-// byte for byte in HWC order against the full 4-channel render)
+// byte for byte in HWC order against the full 4-channel render; also 0: the
+// bytes by which mirrors fed only the reported rectangle / blocks differ from
+// their slot, and the bytes a render stores outside the blocks it reports;
+// mask_share / span_mask_share: the mean share of the frame those blocks
+// cover, and the blocks of both frames' spans)
 //
 // Every frame it publishes, on a bound PUSH socket with SNDHWM/LINGER/
 // IMMEDIATE as btb.DataPublisher does (reference: btb/publisher.py:21-43),
@@ -239,41 +243,86 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
   // would be told about (changed_rect: descriptor element 10): it must stay
   // equal to the slot
   std::vector<std::vector<uint8_t>> mirrors(kSlots, std::vector<uint8_t>(n));
+  // and one updated only inside the blocks the render reports (element 11)
+  std::vector<std::vector<uint8_t>> block_mirrors(kSlots, std::vector<uint8_t>(n));
   const int mc = planar ? 3 : r.channels();      // channels of the bytes a rectangle covers (rgb_a: the RGB part)
   const bool lower_left = a.origin == "lower-left";
-  double t_full = 0, t_inc = 0;
-  long long mismatches = 0, mirror_mismatches = 0;
+  const int W = r.width(), H = r.height();
+  const int band_rows = blocks::band_rows_for(H), nbands = blocks::bands(H, band_rows);
+  int band_log2 = 0;
+  while ((1 << band_log2) < band_rows) ++band_log2;
+  const bool blocks_ok = blocks::geometry_ok(H, W, band_rows);   // else: no masks, the block figures stay 0
+  // visits the bytes [o, o + len) of every set (inside) or clear block of `mask`
+  auto for_blocks = [&](const uint16_t* mask, bool inside, auto&& f) {
+    for (int y = 0; y < H; ++y)
+      for (int c = 0; c < W / blocks::kBlockCols; ++c)
+        if (((mask[y >> band_log2] >> c) & 1) == (inside ? 1 : 0))
+          f((size_t(y) * W + size_t(c) * blocks::kBlockCols) * size_t(mc), size_t(blocks::kBlockCols) * size_t(mc));
+  };
+  std::vector<uint16_t> span_prev(size_t(kSlots) * blocks::kMaxBands, uint16_t(0));
+  std::vector<uint8_t> probe(n);
+  double t_full = 0, t_inc = 0, mask_share = 0, span_share = 0;
+  long long mismatches = 0, mirror_mismatches = 0, block_mirror_mismatches = 0, stores_outside = 0, masked = 0;
   uint64_t h = 1469598103934665603ull;   // FNV-1a over every incremental frame
   int frame = a.frame_start;
   for (long long i = 0; i < a.bench; ++i) {
     pose(frame);
     frame = frame >= a.frame_end ? a.frame_start : frame + 1;
     const uint8_t* full = fulls[size_t(i % kSlots)].data();
+    // both renders report their blocks: the same bookkeeping in either timing
+    uint16_t wr_full[blocks::kMaxBands] = {}, wr[blocks::kMaxBands] = {};
+    sim::DirtyRect& rec = dirty[size_t(i % kSlots)];
+    const sim::DirtyRect rec_before = rec;   // (the record only: the slot stays cold)
+    const bool was_known = rec.known;
     auto t0 = std::chrono::steady_clock::now();
-    r.render(scene, fulls[size_t(i % kSlots)].data());
+    r.render(scene, fulls[size_t(i % kSlots)].data(), nullptr, blocks_ok ? wr_full : nullptr, band_log2);
     auto t1 = std::chrono::steady_clock::now();
     uint8_t* out = slots[size_t(i % kSlots)].data();
-    sim::DirtyRect before;
-    const bool was_known = dirty[size_t(i % kSlots)].known;
-    {
-      const sim::DirtyRect& d = dirty[size_t(i % kSlots)];
-      before.x0 = d.x0, before.y0 = d.y0, before.x1 = d.x1, before.y1 = d.y1;
-    }
     if (planar) {
-      if (!dirty[size_t(i % kSlots)].known) fill_alpha_plane(out, npix);
-      planar->render(scene, out, &dirty[size_t(i % kSlots)]);
+      if (!rec.known) fill_alpha_plane(out, npix);
+      planar->render(scene, out, &rec, blocks_ok ? wr : nullptr, band_log2);
     } else {
-      r.render(scene, out, &dirty[size_t(i % kSlots)]);
+      r.render(scene, out, &rec, blocks_ok ? wr : nullptr, band_log2);
     }
     auto t2 = std::chrono::steady_clock::now();
     t_full += std::chrono::duration<double, std::milli>(t1 - t0).count();
     t_inc += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    uint8_t* mir = mirrors[size_t(i % kSlots)].data();
+    if (blocks_ok) {
+      uint16_t cur[blocks::kMaxBands] = {};
+      sim::span_blocks(rec, H, lower_left, band_log2, cur);
+      uint16_t* sp = &span_prev[size_t(i % kSlots) * blocks::kMaxBands];
+      if (was_known) {
+        uint16_t u[blocks::kMaxBands];
+        for (int k = 0; k < nbands; ++k) u[k] = uint16_t(sp[k] | cur[k]);
+        span_share += double(blocks::pixels(u, H, band_rows)) / double(npix);
+        mask_share += double(blocks::pixels(wr, H, band_rows)) / double(npix);
+        ++masked;
+        // no store outside the mask: the slot as it was (the rectangle mirror,
+        // not yet brought up to date), every byte outside the mask replaced by
+        // a sentinel, rendered with a copy of the record the slot had -- with
+        // two sentinels, since a store may write either value
+        for (const uint8_t sentinel : {uint8_t(0xa5), uint8_t(0x5a)}) {
+          std::memcpy(probe.data(), mir, n);
+          for_blocks(wr, false, [&](size_t o, size_t len) { std::memset(probe.data() + o, sentinel, len); });
+          sim::DirtyRect rec_probe = rec_before;
+          (planar ? planar : &r)->render(scene, probe.data(), &rec_probe);
+          for_blocks(wr, false, [&](size_t o, size_t len) {
+            for (size_t k = o; k < o + len; ++k) stores_outside += probe[k] != sentinel;
+          });
+        }
+      }
+      std::memcpy(sp, cur, sizeof(cur));
+      uint8_t* bm = block_mirrors[size_t(i % kSlots)].data();
+      if (!was_known) std::memcpy(bm, out, n);
+      else for_blocks(wr, true, [&](size_t o, size_t len) { std::memcpy(bm + o, out + o, len); });
+      for (size_t k = 0; k < n; ++k) block_mirror_mismatches += bm[k] != out[k];
+    }
     {
-      uint8_t* mir = mirrors[size_t(i % kSlots)].data();
       if (!was_known) {
         std::memcpy(mir, out, n);   // a slot's first frame is taken whole
       } else {
-        const sim::StoredRect c = sim::changed_rect(before, dirty[size_t(i % kSlots)], r.height(), lower_left);
+        const sim::StoredRect c = sim::changed_rect(rec_before, rec, r.height(), lower_left);
         for (int y = c.y0; !c.empty() && y <= c.y1; ++y) {
           const size_t o = (size_t(y) * r.width() + size_t(c.x0)) * size_t(mc);
           std::memcpy(mir + o, out + o, size_t(c.x1 - c.x0 + 1) * size_t(mc));
@@ -290,10 +339,13 @@ int bench(const Args& a, sim::Scene& scene, sim::Renderer& r, Pose& pose, sim::R
     }
   }
   std::printf("{\"frames\": %lld, \"full_ms\": %.4f, \"incremental_ms\": %.4f, \"mismatched_bytes\": %lld, "
-              "\"mirror_mismatched_bytes\": %lld, \"checksum\": \"%016llx\", \"isa\": \"%s\"}\n",
-              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, mirror_mismatches, (unsigned long long)h,
-              sim::raster_isa());
-  return mismatches == 0 && mirror_mismatches == 0 ? 0 : 1;
+              "\"mirror_mismatched_bytes\": %lld, \"block_mirror_mismatched_bytes\": %lld, "
+              "\"stores_outside_mask\": %lld, \"mask_share\": %.4f, \"span_mask_share\": %.4f, "
+              "\"checksum\": \"%016llx\", \"isa\": \"%s\"}\n",
+              a.bench, t_full / a.bench, t_inc / a.bench, mismatches, mirror_mismatches, block_mirror_mismatches,
+              stores_outside, mask_share / double(std::max(masked, 1ll)), span_share / double(std::max(masked, 1ll)),
+              (unsigned long long)h, sim::raster_isa());
+  return mismatches == 0 && mirror_mismatches == 0 && block_mirror_mismatches == 0 && stores_outside == 0 ? 0 : 1;
 }
 
 }  // namespace
@@ -396,14 +448,12 @@ int main(int argc, char** argv) {
   // with by THIS producer (0: never, or not to be relied on) -- kept here, not
   // read back from the slot word, which a lease reclaim bumps
   std::vector<uint32_t> slot_gen(seg ? size_t(a.shm_slots) : 0, 0u);
-  // kWantSlotBlocks (shmring.h): the blocks each slot's last frame touched
-  // (sim::span_blocks of the record in slot_dirty); a frame's report is that
-  // OR-ed with its own
+  // kWantSlotBlocks (shmring.h): a frame's report is the blocks its render
+  // stored into (Renderer::render's `written`, and the stamp's)
   const int band_rows = blocks::band_rows_for(H), nbands = blocks::bands(H, band_rows);
   int band_log2 = 0;
   while ((1 << band_log2) < band_rows) ++band_log2;
   const bool blocks_ok = seg && !tiled && incremental && blocks::geometry_ok(H, W, band_rows);
-  std::vector<uint16_t> slot_mask(blocks_ok ? size_t(a.shm_slots) * size_t(nbands) : 0, uint16_t(0));
   const size_t npix = size_t(W) * H;
   const auto t_start = std::chrono::steady_clock::now();
   auto next_due = t_start;
@@ -417,7 +467,7 @@ int main(int argc, char** argv) {
   // descriptor, publish, faults, send), strictly in dispatch order.  With T
   // workers up to T + 1 frames are between front half and retire, each in a
   // slot of its own, so what a consumer receives does not depend on T (only
-  // the slot indices may).  slot_dirty, slot_layout, slot_gen and slot_mask
+  // the slot indices may).  slot_dirty, slot_layout and slot_gen
   // are touched for a slot only between its acquire and its retire, by the
   // one frame that holds it.  T = 1 renders on the main thread: the loop of a
   // single-threaded producer.  tile16 frames build on one another: T = 1.
@@ -545,7 +595,9 @@ int main(int argc, char** argv) {
     }
     std::unique_ptr<sim::Renderer>& r = planar ? rs.rgb : rs.hwc;
     if (!r) r.reset(new sim::Renderer(s, planar ? 3 : C, lower_left));
-    r->render(s, pixels, dirty);
+    const bool masked = blocks_ok && dirty;
+    if (masked) std::memset(j.mask, 0, sizeof(j.mask));
+    r->render(s, pixels, dirty, masked ? j.mask : nullptr, band_log2);
     if (a.stamp) {
       // bytes 0..15 of the stored image (first stored row): 'B','T', btid (u16 LE),
       // 4 zero bytes, seq (u64 LE) -- lets tests match every decoded image to its metadata
@@ -559,11 +611,13 @@ int main(int argc, char** argv) {
           std::memcpy(pixels + 3 * p, st + 4 * p, 3);
           pixels[npix * 3 + size_t(p)] = st[4 * p + 3];
           const int row = p / W, col = p % W;   // stored row / column of pixel p
-          if (dirty) dirty->add(lower_left ? H - 1 - row : row, col, col);
+          if (dirty) dirty->foreign(lower_left ? H - 1 - row : row, col, col);
+          if (masked) j.mask[row >> band_log2] |= blocks::column_bits(col, col);
         }
       } else {
         std::memcpy(pixels, st, sizeof(st));
-        if (dirty) dirty->add(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+        if (dirty) dirty->foreign(lower_left ? H - 1 : 0, 0, (int(sizeof(st)) + C - 1) / C - 1);
+        if (masked) j.mask[0] |= blocks::column_bits(0, (int(sizeof(st)) + C - 1) / C - 1);
       }
     }
     if (tiled) {
@@ -578,15 +632,9 @@ int main(int argc, char** argv) {
                           tiled_dirty.x1, slot_bytes);
     }
     if (j.delta_known) j.changed = sim::changed_rect(before, *dirty, H, lower_left);
-    if (blocks_ok && dirty) {
-      // the blocks of this frame's spans (the stamp's pixels among them); what
-      // changed lies in those and in the ones the slot's last frame left
-      uint16_t cur[blocks::kMaxBands] = {};
-      sim::span_blocks(*dirty, H, lower_left, band_log2, cur);
-      uint16_t* prev = &slot_mask[size_t(slot) * size_t(nbands)];
-      for (int k = 0; k < nbands; ++k) j.mask[k] = uint16_t(prev[k] | cur[k]), prev[k] = cur[k];
-      j.has_mask = j.delta_known;
-    }
+    // the mask holds every block this frame's render or stamp stored into:
+    // all else is what the slot held one generation earlier
+    j.has_mask = masked && j.delta_known;
     j.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
   };
 

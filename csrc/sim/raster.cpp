@@ -379,7 +379,7 @@ struct Plane2 {
 
 }  // namespace
 
-void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
+void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty, uint16_t* written, int band_log2) {
   const Camera& cam = s.cam;
   const int W = W_, H = H_, C = C_;
   const Vec3 o = cam.loc;
@@ -390,8 +390,14 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
 
   const bool avx2 = use_avx2();
   auto row_ptr = [&](int y) { return out + size_t(lower_left_ ? (H - 1 - y) : y) * W * C; };
+  // `written`: the blocks of pixels [a, b] of image row y (raster.h); called
+  // for every interval that is stored into
+  auto mark = [&](int y, int a, int b) {
+    if (written) written[(lower_left_ ? H - 1 - y : y) >> band_log2] |= uint16_t((2u << (unsigned(b) >> 6)) - (1u << (unsigned(a) >> 6)));
+  };
   // background bytes back into pixels [a, b] of image row y
   auto restore = [&](int y, int a, int b) {
+    mark(y, a, b);
     uint8_t* r = row_ptr(y);
     const size_t off = size_t(a) * C;
     std::memcpy(r + off, background_.data() + (r - out) + off, size_t(b - a + 1) * C);
@@ -401,6 +407,11 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
   const bool deferred = dirty && dirty->known && !dirty->empty() && dirty->lo.size() == size_t(H) &&
                         dirty->hi.size() == size_t(H) && s.boxes.size() == 1;
   const int old_y0 = deferred ? std::max(dirty->y0, 0) : 0, old_y1 = deferred ? std::min(dirty->y1, H - 1) : -1;
+  // one box: the frame leaves a shadow record (raster.h: DirtyRect::shadow),
+  // and a deferred frame that finds one skips the shadow it says is there
+  const bool record = dirty && s.boxes.size() == 1;
+  const bool keep = deferred && dirty->shadow.size() == size_t(H);
+  if (dirty) prev_shadow_.swap(dirty->shadow);   // (as lo / hi: the arrays go back and forth)
   if (deferred) {
     prev_lo_.swap(dirty->lo);   // (dirty's arrays become this frame's record below)
     prev_hi_.swap(dirty->hi);
@@ -417,6 +428,7 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
     }
   } else {
     std::memcpy(out, background_.data(), background_.size());
+    for (int y = 0; written && y < H; ++y) mark(y, 0, W - 1);
   }
   // deferred: the frame wrote every pixel of [a, b] in row y
   auto cover = [&](int y, int a, int b) {
@@ -442,7 +454,31 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
     touched.hi.swap(dirty->hi);
     touched.lo.assign(size_t(H), 1 << 30);
     touched.hi.assign(size_t(H), -1);
+    touched.shadow.swap(dirty->shadow);
+    touched.shadow.assign(record ? size_t(H) : 0, DirtyRect::ShadowRow());
   }
+  // constant shadow pixels into [a, b] of a stored row; no byte outside them
+  const uint32_t shadow4 = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 | uint32_t(shadow_rgb_[2]) << 16;
+  auto fill_shadow = [&](int y, uint8_t* r, int a, int b) {
+    if (a > b) return;
+    mark(y, a, b);
+    if (C == 4) {
+      // alpha is 255 in the background: one 32-bit pattern per pixel
+      const uint32_t v = shadow4 | 0xff000000u;
+      if (avx2) a += fill_rgba_avx2(r + size_t(a) * 4, b - a + 1, v);
+      for (int x = a; x <= b; ++x) std::memcpy(r + size_t(x) * 4, &v, 4);
+    } else {
+      // packed RGB: one 32-bit store per pixel as well -- its 4th byte
+      // lands on the next pixel's red, which that pixel's store rewrites;
+      // the piece's last pixel is written as 3 bytes
+      const uint32_t v = shadow4 | uint32_t(shadow_rgb_[0]) << 24;
+      if (avx2) a += fill_rgb_avx2(r + size_t(a) * 3, b - a + 1, shadow_pat3_);
+      if (a > b) return;
+      for (int x = a; x < b; ++x) std::memcpy(r + size_t(x) * 3, &v, 4);
+      uint8_t* p = r + size_t(b) * 3;
+      p[0] = shadow_rgb_[0], p[1] = shadow_rgb_[1], p[2] = shadow_rgb_[2];
+    }
+  };
 
   // ---- shadows: each box's shadow hull on the ground plane, projected to
   // the image (a projective map keeps it convex) and span-filled ----
@@ -473,29 +509,26 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
         const int b = std::min(x1, plane_x1_[y]);
         if (a > b) return;
         if (deferred) cover(y, a, b);
-        if (C == 4) {
-          // alpha is 255 in the background: one 32-bit pattern per pixel
-          const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
-                             uint32_t(shadow_rgb_[2]) << 16 | 0xff000000u;
-          if (avx2) a += fill_rgba_avx2(r + size_t(a) * 4, b - a + 1, v);
-          for (int x = a; x <= b; ++x) std::memcpy(r + size_t(x) * 4, &v, 4);
-        } else {
-          // packed RGB: one 32-bit store per pixel as well -- its 4th byte
-          // lands on the next pixel's red, which that pixel's store rewrites;
-          // the span's last pixel is written as 3 bytes
-          const uint32_t v = uint32_t(shadow_rgb_[0]) | uint32_t(shadow_rgb_[1]) << 8 |
-                             uint32_t(shadow_rgb_[2]) << 16 | uint32_t(shadow_rgb_[0]) << 24;
-          if (avx2) a += fill_rgb_avx2(r + size_t(a) * 3, b - a + 1, shadow_pat3_);
-          if (a > b) return;
-          for (int x = a; x < b; ++x) std::memcpy(r + size_t(x) * 3, &v, 4);
-          uint8_t* p = r + size_t(b) * 3;
-          p[0] = shadow_rgb_[0], p[1] = shadow_rgb_[1], p[2] = shadow_rgb_[2];
+        if (record) touched.shadow[size_t(y)].a = a, touched.shadow[size_t(y)].b = b;
+        // what the previous frame's fill covered and its faces did not reach
+        // is shadow already: [k0, k1] of the old fill lies in [a, b], and
+        // the old face extent [f0, f1] cuts it into at most two kept pieces
+        const DirtyRect::ShadowRow none;
+        const DirtyRect::ShadowRow& ps = keep ? prev_shadow_[size_t(y)] : none;
+        const int k0 = std::max(a, ps.a), k1 = std::min(b, ps.b);
+        if (k0 > k1) {
+          fill_shadow(y, r, a, b);
+          return;
         }
+        fill_shadow(y, r, a, k0 - 1);
+        if (ps.f0 <= ps.f1) fill_shadow(y, r, std::max(k0, ps.f0), std::min(k1, ps.f1));
+        fill_shadow(y, r, k1 + 1, b);
         return;
       }
       // per-pixel test: no interval to record (one box: this span is the
       // row's first write of the frame)
       if (deferred) restore_row_first(y);
+      mark(y, x0, x1);
       for (int x = x0; x <= x1; ++x) {
         if (pxy[2 * x] != pxy[2 * x]) continue;   // not on the ground plane
         uint8_t* p = r + size_t(x) * C;
@@ -567,6 +600,11 @@ void Renderer::render(const Scene& s, uint8_t* out, DirtyRect* dirty) {
             touched.add(y, x0, x1);
             if (need_depth) depth_rect_.add(y, x0, x1);
             if (deferred) cover(y, x0, x1);
+            if (record) {
+              DirtyRect::ShadowRow& sr = touched.shadow[size_t(y)];
+              sr.f0 = std::min(sr.f0, x0), sr.f1 = std::max(sr.f1, x1);
+            }
+            mark(y, x0, x1);
             uint8_t* r = row_ptr(y);
             const double yc = y + 0.5;
             const float I0 = float(ip.a * (x0 + 0.5) + ip.b * yc + ip.c), dI = float(ip.a);

@@ -87,11 +87,27 @@ Scene falling_cubes_scene();
 // With `lo` / `hi` sized to the image height, each row also keeps the span
 // it wrote (a box and its shadow cover ~57 % of their bounding rectangle, so
 // a restore over the row spans moves that much less memory).
+// `shadow` (sized to the image height by a render of a one-box scene, else
+// empty) keeps what lets the next render leave shadow bytes alone that are
+// shadow already: per image row the interval [a, b] the frame's shadow fill
+// covered on a plane_dense_ row (a > b: none) and the extent [f0, f1] of its
+// face spans.  After the frame every pixel of [a, b] outside [f0, f1] holds
+// the shadow colour.  Whoever writes into the buffer besides render() calls
+// foreign(): that row's record is dropped.
 struct DirtyRect {
+  struct ShadowRow {
+    int a = 1, b = 0, f0 = 1 << 30, f1 = -1;
+  };
   int x0 = 1 << 30, y0 = 1 << 30, x1 = -1, y1 = -1;
   bool known = false;
   std::vector<int> lo, hi;   // per image row [lo, hi]; empty = rectangle only
+  std::vector<ShadowRow> shadow;
   bool empty() const { return x1 < x0 || y1 < y0; }
+  // pixels [a, b] of image row y were written by someone other than render()
+  void foreign(int y, int a, int b) {
+    add(y, a, b);
+    if (!shadow.empty()) shadow[static_cast<unsigned>(y)] = ShadowRow();
+  }
   void reset() { x0 = y0 = 1 << 30, x1 = y1 = -1; }
   void add(int y, int a, int b) {
     y0 = y < y0 ? y : y0, y1 = y > y1 ? y : y1;
@@ -153,8 +169,16 @@ class Renderer {
  public:
   Renderer(const Scene& s, int channels, bool lower_left);
   // dirty: the rectangle `out`'s previous frame left (updated to this
-  // frame's); nullptr = `out` holds anything, copy the whole background
-  void render(const Scene& s, uint8_t* out, DirtyRect* dirty = nullptr);
+  // frame's); nullptr = `out` holds anything, copy the whole background.
+  // written: the blocks (csrc/common/block_mask.h; band_rows = 1 << band_log2,
+  // W <= 1024) that a store of this call touched, transient stores included,
+  // OR-ed into written[ceil(H / band_rows)] in STORED rows; the caller clears
+  // it.  Every byte outside them is what `out` held before the call.  On a
+  // buffer of known content that is less than the blocks of both frames'
+  // spans (span_blocks): shadow pixels the previous frame left as shadow are
+  // not stored again.  Unknown content: every block.
+  void render(const Scene& s, uint8_t* out, DirtyRect* dirty = nullptr, uint16_t* written = nullptr,
+              int band_log2 = 0);
   int width() const { return W_; }
   int height() const { return H_; }
   int channels() const { return C_; }
@@ -186,6 +210,7 @@ class Renderer {
   std::vector<int> cover_;               // per row kMaxCover x [x0, x1]
   std::vector<uint8_t> cover_n_;         // per row: intervals recorded, or kRowRestored
   std::vector<int> prev_lo_, prev_hi_;   // the previous frame's row spans while this frame draws
+  std::vector<DirtyRect::ShadowRow> prev_shadow_;   // and its shadow record (DirtyRect::shadow)
 };
 
 // Which fill bodies render() uses: "avx2" (8 tone-table indices per op, a
